@@ -17,12 +17,17 @@ tasks, ONE env stream replicated on every rank, GPI maxima all-reduced (MAX) ove
 step graphs -- weak scaling in source tasks; N independent 8-head replicas are timed beside it
 (`replicas`).  See DESIGN.md §7.
 
-`other_workloads` (N=1 only; --no-other skips it) times the other one-GPU BASELINE configs through
+A plain run (`python bench.py --gpus 1 --steps K --warmup W`) sets up, warms up, times the K steps,
+writes the loop's state if `--dump-outputs DIR` is given and prints the line; its `roofline`,
+`repeats`, `sharded*`, `other_workloads` and `cpu_baseline` keys are null.  `--full` adds those
+side legs, described below, after the timed window.
+
+`other_workloads` (--full, N=1 only; --no-other skips it) times the other one-GPU BASELINE configs through
 the same native runner: the active-task schedule of sfdqn.py (C2 shape), Hopper TSF-DQN (C3) and
 TSF-DQN with 100 planar layers (C5's per-GPU work); `--workload hopper-tsf[-nf]` makes one of
 them the measured line instead.
 
-Prints ONE JSON line on rank 0.  `roofline` is for the dominant kernel kind, measured live
+Prints ONE JSON line on rank 0.  `roofline` (--full) is for the dominant kernel kind, measured live
 in this process with HIP events (libsfx instrumentation, eager launches) right after the
 timed region; `cpu_baseline` times the CPU oracle (oracle/ref_cpu.py) on a bounded sample
 of the same workload on this box's host cores.
@@ -59,8 +64,14 @@ def parse():
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=None,
                    help="ranks (one per GPU); N > 1 without WORLD_SIZE: this process launches the N ranks")
-    p.add_argument("--steps", type=int, default=2000)
+    p.add_argument("--steps", type=int, default=2000, help="timed env steps (the headline window)")
     p.add_argument("--warmup", type=int, default=200)
+    p.add_argument("--full", action="store_true",
+                   help="after the headline also run the side legs: the repeats, the prof window and roofline, the "
+                        "sharded legs, the other one-GPU workloads and the CPU baseline (each with its own switch below)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write the state the timed loop left (what its caller reads back) as "
+                        "DIR/<name>.npy (rank 0)")
     p.add_argument("--schedule", choices=["all", "active"], default="all")
     p.add_argument("--loop", choices=["native", "python"], default="native",
                    help="native: libsfx's C++ env-step runner (pipelined graphs); python: sfx.runner.EnvLoop")
@@ -588,6 +599,44 @@ def unskipped_window(args, device, prof_steps: int, warmup: int = 200) -> dict:
     return {"stats": stats, "skipped": skipped, "steps": prof_steps}
 
 
+DUMP_MAX_ELEMS = 4_000_000  # per array (16 MB of float32); the arrays below stay under 64 MB together
+
+
+def dump_outputs(path: str, args, eng, loop, native: bool) -> dict:
+    """--dump-outputs: what the timed loop left behind after its last step, as its caller reads it
+    back -- every head's online and target ψ parameters [T, P], the reward weights w [T, d], for
+    the TSF workloads g [T, Pg] and h [Ph], the GPI selection for the next env step (source task,
+    greedy action) and the GPI counters [T, T] -- one float32 / float64 DIR/<name>.npy each.  An
+    array of more than DUMP_MAX_ELEMS elements is written as a fixed sample of its flattened
+    elements (indices drawn once from numpy's default_rng(0), sorted).  The inputs (initial heads,
+    env and replay streams) depend only on the arguments, so two builds run with the same arguments
+    can be compared array for array."""
+    T = eng.T
+    arrays = {"psi_online": np.stack([eng.get_head(t, 0).numpy() for t in range(T)]),
+              "psi_target": np.stack([eng.get_head(t, 1).numpy() for t in range(T)]),
+              "w": np.stack([eng.get_w(t)[0].numpy() for t in range(T)])}
+    if args.tsf_K is not None:
+        arrays["g"] = np.stack([eng.tsf_get_g(t)[0].numpy() for t in range(T)])
+        arrays["h"] = eng.tsf_get_h().numpy()
+    if native:
+        arrays["next_selection"] = np.asarray(loop.action(), dtype=np.float64)
+        arrays["gpi_counters"] = loop.gpi_counters().astype(np.float64)
+    else:
+        arrays["next_selection"] = np.asarray(loop._greedy(), dtype=np.float64)
+        arrays["gpi_counters"] = loop.gpi_counters.astype(np.float64)
+        arrays["losses"] = loop.losses.detach().cpu().numpy()
+    os.makedirs(path, exist_ok=True)
+    written = {}
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+        if a.size > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_ELEMS, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), a)
+        written[name] = list(a.shape)
+    return written
+
+
 def launch_ranks(n: int, argv=None, dry_run: bool = False) -> int:
     """`bench.py --gpus N` as its own launcher (N > 1 and no WORLD_SIZE in the environment): start
     N rank processes of this script, one per GPU, with the torch.distributed env contract
@@ -726,9 +775,13 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     value = world * args.steps / dt
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, args, eng, loop, native)
+    # everything from here to the result line except the N > 1 headline layout is a side leg: --full only
     # spread: the same K-step window timed again (not part of `value`)
     repeats = []
-    if args.repeats > 0:
+    if args.full and args.repeats > 0:
         for _ in range(args.repeats):
             barrier()
             t1 = time.perf_counter()
@@ -736,33 +789,35 @@ def main():
             barrier()
             repeats.append(round(world * args.steps / (time.perf_counter() - t1), 2))
 
-    # live per-kernel durations (HIP events around each launch) for the roofline figure
-    eng.prof_reset()
-    skip0 = eng.skip_stats()
-    eng.prof_enable(True)
-    # the window on CLOCK_MONOTONIC, rocprofv3's timestamp domain: tools/rocprof_window.py averages
-    # the same launches in a kernel trace of this command (profiles/rocprof_window.json)
-    torch.cuda.synchronize(device)
-    t_prof0 = time.monotonic_ns()
-    loop.run(args.prof_steps)
-    stats = eng.prof_collect()
-    t_prof1 = time.monotonic_ns()
-    eng.prof_enable(False)
-    eng.prof_reset()
-    prof_skip = {k: v - skip0[k] for k, v in eng.skip_stats().items()}
-    # the launches' algorithmic bytes (host-side, per launch) count every head of every round; a
-    # skipped policy's tiles return at once, so its bytes are not moved: take them off the kinds
-    # they belong to (device counters over the same steps), so achieved GB/s stays honest
-    launched = sum(v[2] for v in stats.values()) / max(args.prof_steps, 1)
-    skb, skf = skippable_head_bytes(sh, B)
-    nsk = prof_skip["policies_skipped"]
-    for kd, per in (("bwd", skb), ("fwd", skf)):
-        if kd in stats:
-            n_, us_, by_ = stats[kd]
-            stats[kd] = (n_, us_, max(0.0, by_ - nsk * per))
+    if args.full:
+        # live per-kernel durations (HIP events around each launch) for the roofline figure
+        eng.prof_reset()
+        skip0 = eng.skip_stats()
+        eng.prof_enable(True)
+        # the window on CLOCK_MONOTONIC, rocprofv3's timestamp domain: tools/rocprof_window.py averages
+        # the same launches in a kernel trace of this command (profiles/rocprof_window.json)
+        torch.cuda.synchronize(device)
+        t_prof0 = time.monotonic_ns()
+        loop.run(args.prof_steps)
+        stats = eng.prof_collect()
+        t_prof1 = time.monotonic_ns()
+        eng.prof_enable(False)
+        eng.prof_reset()
+        prof_skip = {k: v - skip0[k] for k, v in eng.skip_stats().items()}
+        # the launches' algorithmic bytes (host-side, per launch) count every head of every round; a
+        # skipped policy's tiles return at once, so its bytes are not moved: take them off the kinds
+        # they belong to (device counters over the same steps), so achieved GB/s stays honest
+        launched = sum(v[2] for v in stats.values()) / max(args.prof_steps, 1)
+        skb, skf = skippable_head_bytes(sh, B)
+        nsk = prof_skip["policies_skipped"]
+        for kd, per in (("bwd", skb), ("fwd", skf)):
+            if kd in stats:
+                n_, us_, by_ = stats[kd]
+                stats[kd] = (n_, us_, max(0.0, by_ - nsk * per))
 
     unsk = None
-    if world == 1 and args.schedule == "all" and args.tsf_K is None and rank == 0 and args.prof_steps > 0:
+    if (args.full and world == 1 and args.schedule == "all" and args.tsf_K is None and rank == 0 and
+            args.prof_steps > 0):
         unsk = unskipped_window(args, device, args.prof_steps)
     sharded = replicas = sharded_rccl1 = None
     layout = "single" if world == 1 else f"replica{world}"
@@ -780,7 +835,7 @@ def main():
             value = sharded["value"]
             dt = sharded["ms_per_step"] * args.steps / 1000.0
             layout = f"shard{world}"
-    elif args.shard_steps > 0 and args.schedule == "all":
+    elif args.full and args.shard_steps > 0 and args.schedule == "all":
         # the same window of training as the headline (its warmup, then its step count), so the two
         # rates compare like for like (the all-task rate rises as more speculative rounds skip)
         sharded = bench_sharded(args, world, rank, device, barrier, dist, steps=max(args.steps, args.shard_steps),
@@ -796,7 +851,7 @@ def main():
                 sharded_rccl1 = {"error": repr(e)[:400]}
             finally:
                 os.environ.pop("SFX_RCCL_WORLD1", None)
-    elif args.shard_steps > 0 and args.schedule == "tsf":
+    elif args.full and args.shard_steps > 0 and args.schedule == "tsf":
         sharded = bench_sharded_tsf(args, world, rank, device, barrier, dist)
         if world == 1 and not args.via_host:
             os.environ["SFX_RCCL_WORLD1"] = "1"  # the collectives really issued, at one rank
@@ -809,7 +864,8 @@ def main():
 
     workload = (f"reacher17-{args.schedule}-T{T}-B{B}" if args.tsf_K is None else
                 f"hopper11-tsf{'-nf' + str(args.tsf_K) if args.tsf_K else ''}-T{T}-B{B}")
-    if rank == 0:
+    roofline = None
+    if rank == 0 and args.full:
         kind = max(stats, key=lambda k: stats[k][1])
         n, us, by = stats[kind]
         avg_us = us / max(n, 1)
@@ -891,12 +947,13 @@ def main():
                                        "1024 SIMDs); executed = MOPS_F32/BF16 x 512 FLOPs / live launch / peak")
         roofline["per_step"]["flops_per_env_step"] = round(T * f + T * B * f + U * 4 * B * f)
         roofline["per_step"]["compute_frac"] = round((T * f + T * B * f + U * 4 * B * f) * per_gpu_rate / peak_c, 5)
+    if rank == 0:
         spec_stats = eng.step_stats()
         spec_stats.update(eng.skip_stats())
         if native:
             spec_stats.update(loop.stats())
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             # the reference's CPU path on the box's cores.  The value is the best of
             # the thread counts this job may use (its CPU share: 8 and 16 threads timed), for both
             # schedules; the share is the ceiling -- more threads would take other jobs' cores
@@ -921,7 +978,7 @@ def main():
                 cpu["c1_cartpole4_all_T2_B32"] = {k: v for k, v in cpu_baseline(c1, 5.0).items()
                                                   if k in ("value", "unit", "cores", "kind", "sample")}
         other = None
-        if world == 1 and args.other and args.tsf_K is None and args.schedule == "all":
+        if args.full and world == 1 and args.other and args.tsf_K is None and args.schedule == "all":
             other = bench_other_workloads(args, device)
         out = {
             "metric": METRIC if args.tsf_K is None else
@@ -950,6 +1007,8 @@ def main():
             "replicas": replicas,
             "other_workloads": other,
             "cpu_baseline": cpu,
+            "full": args.full,
+            "dumped_outputs": dumped,
         }
         print(json.dumps(out), flush=True)
     if dist is not None:

@@ -37,6 +37,13 @@ def test_one_gpu_runs_in_process():
     assert len(lines) == 1 and lines[0]["RANK"] is None and lines[0]["gpus"] == 1
 
 
+def test_full_and_dump_outputs_are_options(tmp_path):
+    # the dry run parses the whole command line; it touches no GPU and writes nothing
+    res = _run(["--gpus", "1", "--steps", "7", "--warmup", "2", "--full", "--dump-outputs", str(tmp_path / "out")])
+    assert res.returncode == 0, res.stderr
+    assert json.loads(res.stdout.splitlines()[-1])["gpus"] == 1 and not (tmp_path / "out").exists()
+
+
 def test_torchrun_world_must_match_gpus():
     # under an outside launcher (WORLD_SIZE set) the flag is checked, not re-launched
     res = _run(["--gpus", "3"], WORLD_SIZE="2", RANK="0", LOCAL_RANK="0")

@@ -2,6 +2,7 @@
 to sfx's libraries and leaves the user's agents, utils and tasks alone; the ψ architecture is
 recognised or rejected; the library keeps the reference's bookkeeping; compute fails loudly
 without a HIP device."""
+import json
 import os
 import sys
 import textwrap
@@ -11,7 +12,7 @@ import torch
 
 from tests.golden.recipe import AgentTask, agent_psi_lambda
 
-REF = "/root/reference/source"
+LAYOUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_layout.json")
 
 
 def _uninstall():
@@ -105,22 +106,34 @@ def test_install_binds_the_sf_library_only(checkout):
         assert agent.update_successor(None, 0) is None
 
 
-def test_install_on_the_reference_checkout():
-    """The hook on the real reference tree (this container only): its scripts' imports resolve
-    to sfx's libraries and to the reference's own agents."""
-    if not os.path.isdir(REF):
-        pytest.skip("reference checkout not present")
-    import types
+def _reference_layout_tree(root):
+    """A stand-in for the reference checkout: every module file of its source tree by name
+    (tests/golden/reference_layout.json), empty but for the classes -- and, on the agents, the
+    methods -- that the binding looks for."""
+    with open(LAYOUT) as f:
+        layout = json.load(f)
+    for rel in layout["modules"]:
+        text = "WHO = 'user'\n"
+        for cls, methods in layout["classes"].get(rel, {}).items():
+            text += f"class {cls}:\n    pass\n"
+            for m in methods:
+                text += f"    def {m}(self, *args, **kwargs):\n        return 'user {m}'\n"
+        p = root / rel
+        p.parent.mkdir(parents=True, exist_ok=True)
+        p.write_text(text)
+    return layout
 
+
+def test_install_on_the_reference_checkout(tmp_path):
+    """The hook on a tree with the reference checkout's full module layout: its scripts' imports
+    resolve to sfx's libraries and to the checkout's own agents."""
     from sfx import dropin
     from sfx.dropin import bind
 
+    layout = _reference_layout_tree(tmp_path)
+    ref = str(tmp_path)
     _uninstall()
-    tb = types.ModuleType("torch.utils.tensorboard")  # utils/logger.py imports it; not installed here
-    tb.SummaryWriter = object
-    saved_tb = sys.modules.get("torch.utils.tensorboard")
-    sys.modules["torch.utils.tensorboard"] = tb
-    sys.path.insert(0, REF)
+    sys.path.insert(0, ref)
     try:
         dropin.install()
         import agents.sfdqn
@@ -130,15 +143,24 @@ def test_install_on_the_reference_checkout():
         import tsfdqn
 
         assert features.deep.__file__.startswith(dropin.ROOT)
-        assert features.tabular.__file__.startswith(REF) and agents.sfdqn.__file__.startswith(REF)
-        assert tsfdqn.__file__.startswith(REF) and tsfdqn.DeepTSF is bind.SingleFileDeepTSF
+        assert features.tabular.__file__.startswith(ref) and agents.sfdqn.__file__.startswith(ref)
+        assert tsfdqn.__file__.startswith(ref) and tsfdqn.DeepTSF is bind.SingleFileDeepTSF
         assert agents.tsfdqn_sequential.TSFDQN.update_successor is bind.tsf_update_successor
+        # every module of the layout imports: sfx's for the names it replaces, the checkout's otherwise
+        import importlib
+
+        for rel in layout["modules"]:
+            name = rel[:-3].replace("/", ".").removesuffix(".__init__")
+            mod = importlib.import_module(name)
+            ours = name in dropin.OURS or name in dropin.AGENT_ALIASES or name == "features"
+            assert mod.__file__.startswith(dropin.ROOT if ours else ref), name
+            if not ours:
+                assert mod.WHO == "user", name
     finally:
-        sys.path.remove(REF)
-        if saved_tb is None:
-            del sys.modules["torch.utils.tensorboard"]
-        else:
-            sys.modules["torch.utils.tensorboard"] = saved_tb
+        sys.path.remove(ref)
+        for name, mod in list(sys.modules.items()):  # the stand-in's top-level scripts too
+            if (getattr(mod, "__file__", None) or "").startswith(ref):
+                del sys.modules[name]
         _uninstall()
 
 

@@ -12,7 +12,7 @@ TAG=$1; PAIRS=$2; A=$3; B=$4; shift 4
 ARGS="$*"; [ -n "$ARGS" ] || ARGS="--steps 2000 --warmup 200 --repeats 2"
 O=gpurun_out/ab_$TAG; mkdir -p $O
 run() {  # name, settings
-  env $2 timeout -k 10 300 python3 bench.py $ARGS --no-other --no-cpu-baseline --shard-steps 0 > $O/$1.json 2>$O/$1.err || return 1
+  env $2 timeout -k 10 300 python3 bench.py --full $ARGS --no-other --no-cpu-baseline --shard-steps 0 > $O/$1.json 2>$O/$1.err || return 1
   python3 -c "import json,sys;d=json.loads(open(sys.argv[1]).read().splitlines()[-1]);r=d['roofline'];print(sys.argv[2], d['value'], (d.get('repeats') or {}).get('values'), r['kernel'], r['avg_launch_us'])" $O/$1.json $1
 }
 for i in $(seq 1 $PAIRS); do

@@ -9,4 +9,4 @@ timeout -k 10 1000 python -u -m pytest ${TESTS:-tests} -x -q -m gpu --timeout 20
 for p in $PROBE; do
   SFX_PROBE_PREC=$p SFX_LIB=$PWD/deep-successor-features-for-transfer_amd/sfx/libsfx_probe.so timeout -k 10 150 python3 tools/probe_run.py 30 > $O/probe_$p.txt 2>&1 || exit 1
 done
-timeout -k 10 500 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench.log 2>&1; rc=$?; tail -c 400 $O/bench.log; exit $rc
+timeout -k 10 500 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench.log 2>&1; rc=$?; tail -c 400 $O/bench.log; exit $rc

@@ -2,7 +2,7 @@
 """Average duration of the roofline kernel's launches inside bench.py's prof window, from a
 rocprofv3 --kernel-trace of the same command.
 
-bench.py times the dominant kernel kind live with HIP events over `--prof-steps` steps after the
+With --full, bench.py times the dominant kernel kind live with HIP events over `--prof-steps` steps after the
 timed window and its repeats, and prints that window's CLOCK_MONOTONIC bounds and launch count
 (roofline.prof_window).  rocprofv3 stamps dispatches on the same clock, so the dispatches of that
 kind starting and ending inside the bounds are the same launches.
@@ -43,7 +43,7 @@ def main():
            "live_launches": win["launches"], "live_avg_us": roof["avg_launch_us"],
            "run_launches": n_run, "run_avg_us": ns_run / n_run / 1e3 if n_run else None,
            "window_steps": win["steps"],
-           "source": "rocprofv3 --kernel-trace of `python3 bench.py --no-cpu-baseline --no-other --shard-steps 0` "
+           "source": "rocprofv3 --kernel-trace of `python3 bench.py --full --no-cpu-baseline --no-other --shard-steps 0` "
                      "(default steps / warmup / repeats / prof-steps); window = the bench's prof window bounds"}
     json.dump(res, open(out, "w"), indent=1)
     print(json.dumps(res))
