@@ -37,6 +37,8 @@
 #include "sfx_gpiw.h"
 #include "sfx_tsf.h"
 #include "sfx_phi.h"
+#include "sfx_phiw.h"
+#include "sfx_tsfphi.h"
 #include "../../include/sfx.h"
 
 using namespace sfx;
@@ -349,10 +351,10 @@ void launch(sfx_handle* h, int kind, double bytes, void (*kern)(KArgs...), dim3 
 
 // graph ops of the library's entry points (sfx_gpi 1, sfx_select_action 2, sfx_update 3,
 // sfx_step_all / sfx_update_all* 5, sfx_successors 21, sfx_test_actions 26, TSF 20 / 22-24,
-// learned φ 30): the first call with a new key runs eagerly (run_graph)
+// learned φ 30 / 31): the first call with a new key runs eagerly (run_graph)
 bool eager_first_sight(int op) {
   return op == 1 || op == 2 || op == 3 || op == 5 || op == 21 || op == 26 || op == 20 || (op >= 22 && op <= 24) ||
-         op == 30;
+         op == 30 || op == 31;
 }
 
 // Capture `body` (which launches on h->stream) into a graph keyed by `key`, then replay

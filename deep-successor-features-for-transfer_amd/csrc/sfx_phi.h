@@ -92,10 +92,50 @@ __global__ __launch_bounds__(256) void k_phi_fwd(PhiArgs A) {
   }
 }
 
+// backward through the net from the output gradient g [B][d] (LDS; gn the second buffer), layer
+// L-1 .. 0: dW, db (Σ over rows) with the fresh-Adam step (CL: gradients clamped to [-1, 1] first,
+// agents/tsfdqn_phi.py:268-270), then dX through the ReLU
+template <bool CL>
+__device__ __forceinline__ void phi_bwd_net(const PhiArgs& A, float* g, float* gn, const AdamC& c1) {
+  const int tid = threadIdx.x, B = A.B, L = A.n_mid + 2;
+  for (int l = L - 1; l >= 0; --l) {
+    const int K = phi_layer_in(A, l), N = phi_layer_out(A, l);
+    float* W = A.p + phi_layer_off(A, l);
+    float* bias = W + (long long)N * K;
+    const float* X = l == 0 ? A.acts + (long long)(L - 1) * B * A.hid : A.acts + (long long)(l - 1) * B * A.hid;
+    const int xs = l == 0 ? A.n_in : A.hid;
+    // dX first (reads W before its update)
+    if (l > 0) {
+      for (int j = tid; j < B * K; j += 256) {
+        const int b = j / K, k = j - b * K;
+        float acc = 0.f;
+        for (int o = 0; o < N; ++o) acc = __builtin_fmaf(g[b * N + o], W[(long long)o * K + k], acc);
+        gn[b * K + k] = X[(long long)b * xs + k] > 0.f ? acc : 0.f;  // ReLU of the layer below
+      }
+    }
+    __syncthreads();
+    for (int j = tid; j < N * K; j += 256) {
+      const int o = j / K, k = j - o * K;
+      float acc = 0.f;
+      for (int b = 0; b < B; ++b) acc = __builtin_fmaf(g[b * N + o], X[(long long)b * xs + k], acc);
+      W[j] = fresh_adam(W[j], CL ? fminf(fmaxf(acc, -1.f), 1.f) : acc, c1);
+    }
+    for (int o = tid; o < N; o += 256) {
+      float acc = 0.f;
+      for (int b = 0; b < B; ++b) acc = __fadd_rn(acc, g[b * N + o]);
+      bias[o] = fresh_adam(bias[o], CL ? fminf(fmaxf(acc, -1.f), 1.f) : acc, c1);
+    }
+    __syncthreads();
+    float* t = g;
+    g = gn;
+    gn = t;
+  }
+}
+
 __global__ __launch_bounds__(256) void k_phi_bwd(PhiArgs A) {
   __shared__ float sg[PHI_B * PHI_HID], sg2[PHI_B * PHI_HID];
   __shared__ float s_w[PHI_IN], s_e[PHI_B];
-  const int tid = threadIdx.x, B = A.B, d = A.d, L = A.n_mid + 2;
+  const int tid = threadIdx.x, B = A.B, d = A.d;
   const AdamC c1 = adam_consts(A.hp, 1);
   if (tid < d) s_w[tid] = A.w[tid];
   __syncthreads();
@@ -138,41 +178,16 @@ __global__ __launch_bounds__(256) void k_phi_bwd(PhiArgs A) {
     *A.lam = ln;
     A.losses[3] = ln;
   }
-  // backward through the net, layer L-1 .. 0: dW, db (Σ over rows), then dX through the ReLU
-  float* g = sg;
-  float* gn = sg2;
-  for (int l = L - 1; l >= 0; --l) {
-    const int K = phi_layer_in(A, l), N = phi_layer_out(A, l);
-    float* W = A.p + phi_layer_off(A, l);
-    float* bias = W + (long long)N * K;
-    const float* X = l == 0 ? A.acts + (long long)(L - 1) * B * A.hid : A.acts + (long long)(l - 1) * B * A.hid;
-    const int xs = l == 0 ? A.n_in : A.hid;
-    // dX first (reads W before its update)
-    if (l > 0) {
-      for (int j = tid; j < B * K; j += 256) {
-        const int b = j / K, k = j - b * K;
-        float acc = 0.f;
-        for (int o = 0; o < N; ++o) acc = __builtin_fmaf(g[b * N + o], W[(long long)o * K + k], acc);
-        gn[b * K + k] = X[(long long)b * xs + k] > 0.f ? acc : 0.f;  // ReLU of the layer below
-      }
-    }
-    __syncthreads();
-    for (int j = tid; j < N * K; j += 256) {
-      const int o = j / K, k = j - o * K;
-      float acc = 0.f;
-      for (int b = 0; b < B; ++b) acc = __builtin_fmaf(g[b * N + o], X[(long long)b * xs + k], acc);
-      W[j] = fresh_adam(W[j], acc, c1);
-    }
-    for (int o = tid; o < N; o += 256) {
-      float acc = 0.f;
-      for (int b = 0; b < B; ++b) acc = __fadd_rn(acc, g[b * N + o]);
-      bias[o] = fresh_adam(bias[o], acc, c1);
-    }
-    __syncthreads();
-    float* t = g;
-    g = gn;
-    gn = t;
-  }
+  phi_bwd_net<false>(A, sg, sg2, c1);
+}
+
+// the φ net's backward from an output gradient in memory (gtop [B][d], sfx_tsfphi.h k_tsfphi_bwd)
+__global__ __launch_bounds__(256) void k_phi_bwd_top(PhiArgs A, const float* gtop) {
+  __shared__ float sg[PHI_B * PHI_HID], sg2[PHI_B * PHI_HID];
+  const AdamC c1 = adam_consts(A.hp, 1);
+  for (int j = threadIdx.x; j < A.B * A.d; j += 256) sg[j] = gtop[j];
+  __syncthreads();
+  phi_bwd_net<true>(A, sg, sg2, c1);
 }
 
 }  // namespace sfx

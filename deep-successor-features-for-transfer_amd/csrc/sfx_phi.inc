@@ -7,13 +7,17 @@ struct sfx_phi_state {
   float* acts = nullptr;  // [n_mid + 2][Mmax][hid] (+ the input block)
   float* phis = nullptr;  // [Mmax][d]
   float lr = 1e-3f;
+  bool wide = false;      // hid > 128: sfx_phiw.h's kernels
+  // TSF-DQN with a learned φ (sfx_tsf_phi_update) and the wide net's backward
+  float *tphi = nullptr, *tt = nullptr, *usum = nullptr;  // [Mmax][d] φ̃, t, u + u'
+  float* gbuf = nullptr;  // [2][Mmax][max(hid, d)] the layers' output gradients (ping-pong)
 };
 
 namespace {
 
 void phi_free(sfx_phi_state* s) {
   if (!s) return;
-  for (float* q : {s->p, s->acts, s->phis})
+  for (float* q : {s->p, s->acts, s->phis, s->tphi, s->tt, s->usum, s->gbuf})
     if (q) (void)hipFree(q);
   delete s;
 }
@@ -39,6 +43,48 @@ PhiArgs phi_args(sfx_handle* h, int pol, int B) {
   return A;
 }
 
+// Buffers that only some updates need, allocated at their first use (outside any capture): gbuf for a
+// wide net's backward and for sfx_tsf_phi_update, tphi / tt / usum for sfx_tsf_phi_update alone.
+int phi_lazy_buffers(sfx_handle* h, bool tsf) {
+  sfx_phi_state* s = h->phi;
+  const size_t bd = (size_t)h->Mmax * h->d, gs = (size_t)2 * h->Mmax * std::max(s->hid, h->d);
+  float** ptrs[4] = {&s->gbuf, &s->tphi, &s->tt, &s->usum};
+  const size_t sizes[4] = {gs, bd, bd, bd};
+  for (int i = 0; i < (tsf ? 4 : 1); ++i) {
+    if (*ptrs[i]) continue;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (hipMalloc((void**)ptrs[i], sizeof(float) * sizes[i]) != hipSuccess ||
+        hipMemset(*ptrs[i], 0, sizeof(float) * sizes[i]) != hipSuccess)
+      SFX_FAIL(SFX_E_HIP, "learned φ: hipMalloc failed");
+  }
+  return SFX_OK;
+}
+
+int phi_setup_common(sfx_handle* h, int n_in, int hid, int n_mid, float lr) {
+  HIPCHK(hipStreamSynchronize(h->stream));
+  if (h->phi) phi_free(h->phi);
+  h->phi = nullptr;
+  clear_graphs(h);  // captured updates carry the freed buffers
+  auto* s = new sfx_phi_state();
+  s->n_in = n_in;
+  s->hid = hid;
+  s->n_mid = n_mid;
+  s->lr = lr;
+  s->wide = hid > PHI_HID;
+  s->P = hid * (n_in + 1) + n_mid * hid * (hid + 1) + h->d * (hid + 1);
+  // the layer-0 input block [Mmax][n_in] sits in the last slot of acts: a slot holds max(hid, n_in) per row
+  const size_t sizes[3] = {(size_t)s->P, (size_t)(n_mid + 2) * h->Mmax * std::max(hid, n_in), (size_t)h->Mmax * h->d};
+  float** ptrs[3] = {&s->p, &s->acts, &s->phis};
+  for (int i = 0; i < 3; ++i)
+    if (hipMalloc((void**)ptrs[i], sizeof(float) * sizes[i]) != hipSuccess ||
+        hipMemset(*ptrs[i], 0, sizeof(float) * sizes[i]) != hipSuccess) {
+      phi_free(s);
+      SFX_FAIL(SFX_E_HIP, "sfx_phi_setup: hipMalloc failed");
+    }
+  h->phi = s;
+  return SFX_OK;
+}
+
 }  // namespace
 
 void phi_release(sfx_handle* h) {
@@ -55,25 +101,18 @@ int sfx_phi_setup(sfx_t h, int width_mul, int n_mid, float lr) {
   const int n_in = 2 * h->n_s + 1, hid = width_mul * n_in;
   if (n_in > PHI_IN || hid > PHI_HID || h->d > PHI_IN || n_mid + 2 > PHI_L || h->Mmax > PHI_B || h->Tg != h->T)
     SFX_FAIL(SFX_E_ARG, "sfx_phi_setup: needs 2 n_s + 1 <= 64, hidden <= 128, d <= 64, max_batch <= 64, unsharded");
-  HIPCHK(hipStreamSynchronize(h->stream));
-  if (h->phi) phi_free(h->phi);
-  h->phi = nullptr;
-  auto* s = new sfx_phi_state();
-  s->n_in = n_in;
-  s->hid = hid;
-  s->n_mid = n_mid;
-  s->lr = lr;
-  s->P = hid * (n_in + 1) + n_mid * hid * (hid + 1) + h->d * (hid + 1);
-  const size_t sizes[3] = {(size_t)s->P, (size_t)(n_mid + 2) * h->Mmax * hid, (size_t)h->Mmax * h->d};
-  float** ptrs[3] = {&s->p, &s->acts, &s->phis};
-  for (int i = 0; i < 3; ++i)
-    if (hipMalloc((void**)ptrs[i], sizeof(float) * sizes[i]) != hipSuccess ||
-        hipMemset(*ptrs[i], 0, sizeof(float) * sizes[i]) != hipSuccess) {
-      phi_free(s);
-      SFX_FAIL(SFX_E_HIP, "sfx_phi_setup: hipMalloc failed");
-    }
-  h->phi = s;
-  return SFX_OK;
+  return phi_setup_common(h, n_in, hid, n_mid, lr);
+}
+
+int sfx_phi_setup_dims(sfx_t h, int hid, int n_mid, float lr) {
+  RC(settle(h));
+  if (!h || hid < 1 || n_mid < 0 || !(lr > 0.f)) SFX_FAIL(SFX_E_ARG, "bad args");
+  touch(h);
+  const int n_in = 2 * h->n_s + 1;
+  if (n_in > PHI_IN || hid > PHIW_HID || h->d > PHI_IN || n_mid + 2 > PHI_L || h->Mmax > PHI_B || h->Tg != h->T)
+    SFX_FAIL(SFX_E_ARG,
+             "sfx_phi_setup_dims: needs 2 n_s + 1 <= 64, hidden <= 2048, d <= 64, max_batch <= 64, unsharded");
+  return phi_setup_common(h, n_in, hid, n_mid, lr);
 }
 
 int sfx_phi_numel(sfx_t h) { return h && h->phi ? h->phi->P : SFX_E_ARG; }
@@ -95,15 +134,91 @@ int sfx_phi_get(sfx_t h, float* params_host) {
   return SFX_OK;
 }
 
-int sfx_phi_update(sfx_t h, int policy, const float* S, const int64_t* a, const float* r, const float* S1,
-                   const float* gamma, int B, int use_gpi, float* bias, float* lambda, float* losses, int64_t* next) {
-  RC(settle(h));
-  if (!h || !h->phi) SFX_FAIL(SFX_E_ARG, "sfx_phi_update: call sfx_phi_setup first");
-  if (!valid_head(h, policy) || B < 1 || B > h->Mmax || !S || !a || !r || !S1 || !gamma || !bias || !lambda || !losses)
-    SFX_FAIL(SFX_E_ARG, "bad args");
+}  // extern "C"
+
+namespace {
+
+// ---- the wide net (sfx_phiw.h): one launch per layer and pass ----
+PhiwLayer phiw_layer(sfx_handle* h, int l, int B, int clamp) {
+  sfx_phi_state* s = h->phi;
+  const int L = s->n_mid + 2;
+  PhiwLayer A{};
+  A.K = l == 0 ? s->n_in : s->hid;
+  A.N = l == L - 1 ? h->d : s->hid;
+  size_t off = 0;
+  for (int j = 0; j < l; ++j) off += (size_t)(j == L - 1 ? h->d : s->hid) * ((j == 0 ? s->n_in : s->hid) + 1);
+  A.W = s->p + off;
+  A.X = l == 0 ? s->acts + (size_t)(L - 1) * B * s->hid : s->acts + (size_t)(l - 1) * B * s->hid;
+  A.Y = l == L - 1 ? s->phis : s->acts + (size_t)l * B * s->hid;
+  const size_t gs = (size_t)h->Mmax * std::max(s->hid, h->d);
+  A.G = s->gbuf + (size_t)((L - 1 - l) & 1) * gs;
+  A.GX = s->gbuf + (size_t)((L - l) & 1) * gs;
+  A.B = B;
+  A.relu = l < L - 1;
+  A.clamp = clamp;
+  A.hp = AdamHP{s->lr, 0.0, h->hp_psi.b1, h->hp_psi.b2, h->hp_psi.eps};
+  return A;
+}
+
+int phiw_forward(sfx_handle* h, int B, const float* S, const int64_t* a, const float* S1) {
+  sfx_phi_state* s = h->phi;
+  const int L = s->n_mid + 2, MT = cdiv(B, 16);
+  launch(h, K_TSF, 4.0 * 2.0 * B * s->n_in, k_phiw_in, dim3(cdiv(B * s->n_in, 256)), dim3(256),
+         s->acts + (size_t)(L - 1) * B * s->hid, S, a, S1, B, h->n_s);
+  LAUNCHCHK();
+  for (int l = 0; l < L; ++l) {
+    const PhiwLayer A = phiw_layer(h, l, B, 0);
+    const double bytes = 4.0 * ((double)A.N * (A.K + 1) + (double)B * (A.K + A.N));
+    const dim3 grid(cdiv(A.N, 16));
+    switch (MT) {
+      case 1: launch(h, K_TSF, bytes, k_phiw_fwd<1>, grid, dim3(64 * PHIW_S), A); break;
+      case 2: launch(h, K_TSF, bytes, k_phiw_fwd<2>, grid, dim3(64 * PHIW_S), A); break;
+      case 3: launch(h, K_TSF, bytes, k_phiw_fwd<3>, grid, dim3(64 * PHIW_S), A); break;
+      default: launch(h, K_TSF, bytes, k_phiw_fwd<4>, grid, dim3(64 * PHIW_S), A); break;
+    }
+    LAUNCHCHK();
+  }
+  return SFX_OK;
+}
+
+// from the output gradient dφ in gbuf's first half: per layer dX (W before its step), then dW + step
+int phiw_backward(sfx_handle* h, int B, int clamp) {
+  sfx_phi_state* s = h->phi;
+  const int L = s->n_mid + 2, MT = cdiv(B, 16);
+  for (int l = L - 1; l >= 0; --l) {
+    const PhiwLayer A = phiw_layer(h, l, B, clamp);
+    const double wb = 4.0 * (double)A.N * A.K, ab = 4.0 * (double)B * (A.K + A.N);
+    if (l > 0) {
+      const dim3 grid(cdiv(A.K, 16));
+      switch (MT) {
+        case 1: launch(h, K_TSF, wb + ab, k_phiw_dx<1>, grid, dim3(64 * PHIW_S), A); break;
+        case 2: launch(h, K_TSF, wb + ab, k_phiw_dx<2>, grid, dim3(64 * PHIW_S), A); break;
+        case 3: launch(h, K_TSF, wb + ab, k_phiw_dx<3>, grid, dim3(64 * PHIW_S), A); break;
+        default: launch(h, K_TSF, wb + ab, k_phiw_dx<4>, grid, dim3(64 * PHIW_S), A); break;
+      }
+      LAUNCHCHK();
+    }
+    const dim3 gw(cdiv(A.N, 16), cdiv(A.K, 256));
+    switch (MT) {
+      case 1: launch(h, K_TSF, 2.0 * wb + ab, k_phiw_dw<1>, gw, dim3(256), A); break;
+      case 2: launch(h, K_TSF, 2.0 * wb + ab, k_phiw_dw<2>, gw, dim3(256), A); break;
+      case 3: launch(h, K_TSF, 2.0 * wb + ab, k_phiw_dw<3>, gw, dim3(256), A); break;
+      default: launch(h, K_TSF, 2.0 * wb + ab, k_phiw_dw<4>, gw, dim3(256), A); break;
+    }
+    LAUNCHCHK();
+  }
+  return SFX_OK;
+}
+
+// DeepSF_PHI.update_successor (transform = 0) / TSFDQN_PHI.update_deep_models (transform = 1)
+int phi_update_impl(sfx_handle* h, int op, int transform, int policy, const float* S, const int64_t* a, const float* r,
+                    const float* S1, const float* gamma, int B, int use_gpi, float* bias, float* lambda, float* losses,
+                    int64_t* next) {
+  if (transform || h->phi->wide) RC(phi_lazy_buffers(h, transform != 0));
   const GraphKey key =
-      make_key(30, {policy, B, use_gpi ? 1 : 0}, h->mask, {S, a, r, S1, gamma, bias, lambda, losses, next});
+      make_key(op, {policy, B, use_gpi ? 1 : 0}, h->mask, {S, a, r, S1, gamma, bias, lambda, losses, next});
   RC(run_graph(h, key, [&]() -> int {
+    sfx_phi_state* s = h->phi;
     PhiArgs A = phi_args(h, policy, B);
     A.S = S;
     A.S1 = S1;
@@ -112,19 +227,53 @@ int sfx_phi_update(sfx_t h, int policy, const float* S, const int64_t* a, const 
     A.wb = bias;
     A.lam = lambda;
     A.losses = losses;
-    const double P = h->phi->P, Bd = B;
-    launch(h, K_TSF, 4.0 * (P + Bd * (h->phi->n_in + (h->phi->n_mid + 1.0) * h->phi->hid + h->d)), k_phi_fwd,
-           dim3(1), dim3(256), A);
-    LAUNCHCHK();
-    // the ψ update with φ as the features: λ-scaled output gradient, fresh Adam, l1 into losses[1]
+    TsfPhiArgs Q{};
+    Q.B = B;
+    Q.d = h->d;
+    Q.n_s = h->n_s;
+    Q.O = h->O;
+    Q.transform = transform;
+    Q.clamp = transform;
+    Q.S = S;
+    Q.S1 = S1;
+    Q.a = a;
+    Q.r = r;
+    if (transform) {
+      Q.g = h->tsf->g + (size_t)policy * h->tsf->Pg;
+      Q.hp = h->tsf->hp;
+    }
+    Q.phis = s->phis;
+    Q.tphi = transform ? s->tphi : s->phis;
+    Q.tt = s->tt;
+    Q.usum = s->usum;
+    Q.dzlast = A.dzlast;
+    Q.gtop = s->gbuf;
+    Q.w = A.w;
+    Q.wb = bias;
+    Q.lam = lambda;
+    Q.losses = losses;
+    Q.hpa = A.hp;
+    const double P = s->P, Bd = B, bd = Bd * h->d;
+    if (s->wide) {
+      RC(phiw_forward(h, B, S, a, S1));
+    } else {
+      launch(h, K_TSF, 4.0 * (P + Bd * (s->n_in + (s->n_mid + 1.0) * s->hid + h->d)), k_phi_fwd, dim3(1), dim3(256), A);
+      LAUNCHCHK();
+    }
+    if (transform) {
+      launch(h, K_TSF, 4.0 * (2.0 * Bd * h->n_s + 4.0 * bd + h->tsf->Pg + h->tsf->Ph), k_tsfphi_fwd, dim3(1), dim3(256),
+             Q);
+      LAUNCHCHK();
+    }
+    // the ψ update with φ (φ̃) as the features: λ-scaled output gradient, fresh Adam, psi_loss into losses[1]
     if (use_gpi)
       RC(run_fwd(h, {{R_S, P_ONLINE, 1, policy, 1}, {R_S1T, P_TARGET, 2, policy, 1}, {R_S1, P_ONLINE, 2, 0, h->T}}, B,
                  S, S1));
     else
       RC(run_fwd(h, {{R_S, P_ONLINE, 1, policy, 1}, {R_S1T, P_TARGET, 2, policy, 1}, {R_S1, P_ONLINE, 2, policy, 1}},
                  B, S, S1));
-    // a freshly built Adam (features/deep_phi.py:163-175 makes one per update): zero moments in
-    // the head's read slot and step 0, which the backward bumps to 1 (its bias corrections)
+    // a freshly built Adam (features/deep_phi.py:163-175, agents/tsfdqn_phi.py:249 make one per update):
+    // zero moments in the head's read slot and step 0, which the backward bumps to 1 (its bias corrections)
     const size_t ro = ((size_t)h->slot(policy) * h->T + policy) * h->P;
     touch(h);
     HIPCHK(hipMemsetAsync(h->am + ro, 0, sizeof(float) * h->P, h->stream));
@@ -137,15 +286,55 @@ int sfx_phi_update(sfx_t h, int policy, const float* S, const int64_t* a, const 
     td.next = next;
     td.next_stride = B;
     td.dz_scale = lambda;
-    RC(run_bwd(h, policy, 1, B, S, h->phi->phis, nullptr, losses, td));
-    launch(h, K_TSF, 4.0 * (3.0 * P + Bd * ((h->phi->n_mid + 1.0) * h->phi->hid + h->phi->n_in + 2.0 * h->d + h->O)),
-           k_phi_bwd, dim3(1), dim3(256), A);
+    RC(run_bwd(h, policy, 1, B, S, Q.tphi, nullptr, losses, td));
+    if (!s->wide && !transform) {
+      launch(h, K_TSF, 4.0 * (3.0 * P + Bd * ((s->n_mid + 1.0) * s->hid + s->n_in + 2.0 * h->d + h->O)), k_phi_bwd,
+             dim3(1), dim3(256), A);
+      LAUNCHCHK();
+      return SFX_OK;
+    }
+    launch(h, K_TSF, 4.0 * (Bd * h->O + 6.0 * bd + (transform ? 2.0 * (h->tsf->Pg + h->tsf->Ph) : 0.0)), k_tsfphi_bwd,
+           dim3(1), dim3(256), Q);
     LAUNCHCHK();
+    if (s->wide) {
+      RC(phiw_backward(h, B, transform));
+    } else {
+      launch(h, K_TSF, 4.0 * (3.0 * P + Bd * ((s->n_mid + 1.0) * s->hid + s->n_in + h->d)), k_phi_bwd_top, dim3(1),
+             dim3(256), A, (const float*)s->gbuf);
+      LAUNCHCHK();
+    }
     return SFX_OK;
   }));
   h->mask ^= 1ull << policy;
   after_update(h, policy);
   return maybe_sync_target(h, policy);
+}
+
+}  // namespace
+
+extern "C" {
+
+int sfx_phi_update(sfx_t h, int policy, const float* S, const int64_t* a, const float* r, const float* S1,
+                   const float* gamma, int B, int use_gpi, float* bias, float* lambda, float* losses, int64_t* next) {
+  RC(settle(h));
+  if (!h || !h->phi) SFX_FAIL(SFX_E_ARG, "sfx_phi_update: call sfx_phi_setup first");
+  if (!valid_head(h, policy) || B < 1 || B > h->Mmax || !S || !a || !r || !S1 || !gamma || !bias || !lambda || !losses)
+    SFX_FAIL(SFX_E_ARG, "bad args");
+  return phi_update_impl(h, 30, 0, policy, S, a, r, S1, gamma, B, use_gpi, bias, lambda, losses, next);
+}
+
+int sfx_tsf_phi_update(sfx_t h, int policy, const float* S, const int64_t* a, const float* r, const float* S1,
+                       const float* gamma, int B, int use_gpi, float* bias, float* lambda, float* losses,
+                       int64_t* next) {
+  RC(settle(h));
+  if (!h) SFX_FAIL(SFX_E_ARG, "bad args");
+  if (!h->phi) SFX_FAIL(SFX_E_ARG, "sfx_tsf_phi_update: call sfx_phi_setup or sfx_phi_setup_dims first");
+  if (!h->tsf) SFX_FAIL(SFX_E_ARG, "sfx_tsf_phi_update: call sfx_tsf_setup(G = d, K = 0) first");
+  if (h->tsf->G != h->d || h->tsf->K != 0)
+    SFX_FAIL(SFX_E_ARG, "sfx_tsf_phi_update: needs sfx_tsf_setup with G = d and K = 0 (g_i, h plain Linear)");
+  if (!valid_head(h, policy) || B < 1 || B > h->Mmax || !S || !a || !r || !S1 || !gamma || !bias || !lambda || !losses)
+    SFX_FAIL(SFX_E_ARG, "bad args");
+  return phi_update_impl(h, 31, 1, policy, S, a, r, S1, gamma, B, use_gpi, bias, lambda, losses, next);
 }
 
 }  // extern "C"

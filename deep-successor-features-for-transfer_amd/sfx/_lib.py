@@ -124,10 +124,12 @@ SIGNATURES = {
     "sfx_tsf_update": (_I, [_VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _VP, _VP]),
     "sfx_tsf_test_action": (_I, [_VP, _VP, _VP, _VP, _VP]),
     "sfx_phi_setup": (_I, [_VP, _I, _I, _F]),
+    "sfx_phi_setup_dims": (_I, [_VP, _I, _I, _F]),
     "sfx_phi_numel": (_I, [_VP]),
     "sfx_phi_load": (_I, [_VP, _VP]),
     "sfx_phi_get": (_I, [_VP, _VP]),
     "sfx_phi_update": (_I, [_VP, _I, _VP, _VP, _VP, _VP, _VP, _I, _I, _VP, _VP, _VP, _VP]),
+    "sfx_tsf_phi_update": (_I, [_VP, _I, _VP, _VP, _VP, _VP, _VP, _I, _I, _VP, _VP, _VP, _VP]),
     "sfx_tsf_test_update": (_I, [_VP, _VP, _VP, _VP, _VP, _F, _VP, _VP, _VP, _VP, _I] + [_F] * 7 + [_VP]),
     "sfx_tsf_test_actions": (_I, [_VP, _VP, _I, _VP, _I, _VP, _I, _VP]),
     "sfx_tsf_test_updates": (_I, [_VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, _I, _VP, _I, _VP, _I, _VP, _F, _F, _F, _VP]),

@@ -32,7 +32,11 @@ modules and ONE 4-group ``torch.optim.Adam`` (tsfdqn.py:255-270: {ψ_i}, {w_i}, 
 
 Learned-φ engines (features/deep_phi.py; ``eng.phi_setup``) add ``phi``: the φ network's packed
 parameters and its configuration (the reference rebuilds its Adam at every update, so there is
-no optimizer state to keep).
+no optimizer state to keep).  ``eng.phi_setup_dims`` (a φ net of any hidden width, e.g.
+main_tsfdqn_phi_torch.py's 2048) records ``{hid, n_mid, lr}`` as its configuration, ``eng.phi_setup``
+``{width_mul, n_mid, lr}`` as before; an engine of TSF-DQN with a learned φ (agents/tsfdqn_phi.py:
+``phi_setup*`` and ``tsf_setup(G = d, K = 0)``) carries both blocks, g_i and h next to φ (their
+persistent Adam moments are unused by that update and stay zero).
 
 So a reference user resumes with ``model.load_state_dict(ck["heads"][t]["model"])`` and
 ``optim.load_state_dict(ck["heads"][t]["optim"])``, and an engine with ``load(eng, path)``.

@@ -4,12 +4,14 @@
 unchanged on libsfx:
 
 * ``features`` becomes sfx's package in front of the user's: ``features.deep``,
-  ``features.deep_sequential``, ``features.deep_sequential_tsf``, ``features.deep_phi`` (learned φ)
-  and ``features.successor`` are sfx's SF libraries (every ψ forward, GPI, TD target, backward and Adam step in the gfx950
+  ``features.deep_sequential``, ``features.deep_sequential_tsf``, ``features.deep_phi`` (learned φ),
+  ``features.deep_tsf_phi`` (TSF-DQN with a learned φ) and ``features.successor`` are sfx's SF libraries (every ψ forward, GPI, TD target, backward and Adam step in the gfx950
   kernels of libsfx.so); every other ``features.*`` module stays the user's;
 * the user's single-file modules ``sfdqn``, ``tsfdqn``, ``tsfdqn_nf`` and
   ``agents.tsfdqn_sequential`` load as they are and are then bound (``sfx.dropin.bind``): their
   library classes become sfx's and the TSF agents' ``update_successor`` one libsfx call;
+  ``agents.sfdqn_phi`` and ``agents.tsfdqn_phi`` load as they are too, the latter's
+  ``TSFDQN_PHI.update_deep_models`` becoming one libsfx call (sfx_tsf_phi_update);
 * ``agents.buffer`` is sfx's ``ReplayBuffer`` (the reference's API over a device-resident ring,
   the same ``np.random`` index draws; ``sfx/dropin/agents/buffer.py``);
 * every other ``agents`` module, ``utils``, ``tasks`` and the scripts themselves are the user's, untouched.
@@ -28,8 +30,8 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 FEATURES = os.path.join(ROOT, "features")
 AGENT_ALIASES = {"agents.buffer": os.path.join(ROOT, "agents", "buffer.py")}
 OURS = ("features.deep", "features.deep_sequential", "features.deep_sequential_tsf", "features.deep_phi",
-        "features.successor")
-BOUND = ("sfdqn", "tsfdqn", "tsfdqn_nf", "agents.tsfdqn_sequential", "agents.sfdqn_phi")
+        "features.deep_tsf_phi", "features.successor")
+BOUND = ("sfdqn", "tsfdqn", "tsfdqn_nf", "agents.tsfdqn_sequential", "agents.sfdqn_phi", "agents.tsfdqn_phi")
 
 
 class _BindingLoader(importlib.abc.Loader):

@@ -8,8 +8,11 @@ user's own modules load unchanged and then applies ``patch``: the library classe
 sfx's, the TSF agents' update_successor becomes one libsfx call (DeepTSF.tsf_update), and their
 test-task methods get_test_action / update_test_reward_mapper (tsfdqn.py:859-997, SURVEY §8f
 rank 1) become libsfx calls too (DeepTSF.tsf_test_action / tsf_test_update), drawing from
-Python's random module exactly where the reference does.  Nothing else of the user's agents is
-touched.
+Python's random module exactly where the reference does.  ``agents.tsfdqn_phi``'s
+``TSFDQN_PHI.update_deep_models`` (:180-288, TSF-DQN with a learned φ) becomes one libsfx call
+(DeepSF_TSF_PHI.tsf_phi_update); its test phase stays the agent's own torch code, run after the
+device's φ net, g_i and h are copied back into the agent's modules.  Nothing else of the user's
+agents is touched.
 """
 from __future__ import annotations
 
@@ -136,6 +139,35 @@ def _phi_synced(method):
     return run
 
 
+def tsf_phi_update_deep_models(self, transitions, phis_model, policy_index, loss_coefficient, use_gpi):
+    """TSFDQN_PHI.update_deep_models (agents/tsfdqn_phi.py:180-288) as one device call
+    (sfx_tsf_phi_update) with the agent's φ net, its active task's g_i and the shared h.  The reference
+    transforms with the ACTIVE task's g whatever policy_index says, and none of its callers passes
+    another policy: anything else is refused.  Returns (loss, psi_loss, phi_loss, loss_coefficient)."""
+    if transitions is None:
+        return None
+    if policy_index != self.task_index:
+        raise NotImplementedError("sfx TSFDQN_PHI.update_deep_models: policy_index must be the active task "
+                                  f"({self.task_index}), got {policy_index}")
+    (phi_model, _, _), _ = phis_model
+    return self.sf.tsf_phi_update(transitions, phi_model, self.g_function, self.h_function, policy_index,
+                                  loss_coefficient, use_gpi)
+
+
+def _tsf_phi_synced(method):
+    """Run the agent's own method after the device's φ net, g_i and h are copied into its modules (the
+    test phase, agents/tsfdqn_phi.py:381-505, runs them in torch)."""
+    @functools.wraps(method)
+    def run(self, *args, **kwargs):
+        sync = getattr(self.sf, "sync_tsf_phi_modules", None)
+        if sync is not None:
+            sync()
+        return method(self, *args, **kwargs)
+
+    run.__sfx_bound__ = True
+    return run
+
+
 def patch(name: str, module) -> None:
     """Bind the user's freshly loaded module ``name`` to sfx (see the module docstring)."""
     if name == "sfdqn":
@@ -149,3 +181,11 @@ def patch(name: str, module) -> None:
         m = getattr(module.SFDQN_PHI, "test_agent", None)
         if m is not None and not getattr(m, "__sfx_bound__", False):
             module.SFDQN_PHI.test_agent = _phi_synced(m)
+    elif name == "agents.tsfdqn_phi":
+        cls = getattr(module, "TSFDQN_PHI", None)
+        if cls is None:  # not the reference's module: nothing to bind
+            return
+        cls.update_deep_models = tsf_phi_update_deep_models
+        m = getattr(cls, "test_agent", None)
+        if m is not None and not getattr(m, "__sfx_bound__", False):
+            cls.test_agent = _tsf_phi_synced(m)

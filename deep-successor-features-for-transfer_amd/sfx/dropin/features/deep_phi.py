@@ -23,20 +23,26 @@ from .deep import _flat, _unflat_into
 LR = 1e-3  # features/deep_phi.py:163-175: every parameter group of the update
 
 
+PHI_NARROW = 128  # hidden widths up to here run sfx_phi_setup's one-workgroup kernels (sfx_phi.h PHI_HID)
+
+
 def _phi_geometry(model: torch.nn.Module, n_s: int, d: int):
-    """(width_mul, n_mid) of main_sfdqn_phi_torch.py's phi_model_lambda net; raises otherwise."""
+    """(hid, n_mid, width_mul) of a phi_model_lambda net (main_sfdqn_phi_torch.py: hid = 2 (2 n_s + 1);
+    main_tsfdqn_phi_torch.py: hid = 2048); width_mul is None when sfx_phi_setup cannot express the net
+    (hid no multiple of 2 n_s + 1, or wider than its kernels) and sfx_phi_setup_dims takes it.  Raises
+    for any other architecture."""
     mods = [m for m in model.modules() if m is not model and not isinstance(m, torch.nn.Sequential)]
     lin = [m for m in mods if isinstance(m, torch.nn.Linear)]
     n_in = 2 * n_s + 1
     ok = len(lin) >= 2 and len(mods) == 2 * len(lin) - 1 and all(l.bias is not None for l in lin)
     ok = ok and all(isinstance(mods[2 * j + 1], torch.nn.ReLU) for j in range(len(lin) - 1))
     hid = lin[0].out_features if lin else 0
-    ok = ok and lin[0].in_features == n_in and hid % n_in == 0 and lin[-1].out_features == d
+    ok = ok and lin[0].in_features == n_in and hid >= 1 and lin[-1].out_features == d
     ok = ok and all(l.in_features == hid and l.out_features == hid for l in lin[1:-1]) and lin[-1].in_features == hid
     if not ok:
-        raise NotImplementedError("sfx DeepSF_PHI: φ net must be Linear(2 n_s + 1, k (2 n_s + 1)) + ReLU, "
+        raise NotImplementedError("sfx DeepSF_PHI: φ net must be Linear(2 n_s + 1, hid) + ReLU, "
                                   f"[Linear(hid, hid) + ReLU]*, Linear(hid, d); got {model}")
-    return hid // n_in, len(lin) - 2
+    return hid, len(lin) - 2, (hid // n_in if hid % n_in == 0 and hid <= PHI_NARROW else None)
 
 
 class _FitWBias(list):
@@ -92,9 +98,12 @@ class DeepSF_PHI(_deep.DeepSF):
     def _phi_engine(self, phi_model, batch):
         eng = self._engine(batch)
         if self._phi_model is None:
-            width_mul, n_mid = _phi_geometry(phi_model, self.inputs, self.n_features)
+            hid, n_mid, width_mul = _phi_geometry(phi_model, self.inputs, self.n_features)
             eng.set_adam(LR, 0.0, LR, 0.0)  # the update's own Adam (features/deep_phi.py:163-175)
-            eng.phi_setup(width_mul, n_mid, LR)
+            if width_mul is not None:
+                eng.phi_setup(width_mul, n_mid, LR)
+            else:  # a width sfx_phi_setup cannot express (main_tsfdqn_phi_torch.py's 2048)
+                eng.phi_setup_dims(hid, n_mid, LR)
             eng.phi_load(_flat(phi_model))
             self._phi_model, self._phi_eng = phi_model, eng
         elif phi_model is not self._phi_model:

@@ -663,6 +663,13 @@ class SFEngine:
         self.phi_numel = lib.sfx_phi_numel(self._h)
         self.phi_cfg = dict(width_mul=int(width_mul), n_mid=int(n_mid), lr=float(lr))
 
+    def phi_setup_dims(self, hid: int = 2048, n_mid: int = 3, lr: float = 1e-3):
+        """The learned φ with its hidden width given directly (main_tsfdqn_phi_torch.py phi_model_lambda:
+        hid 2048, n_mid 3).  hid <= 128 runs phi_setup's kernels, a wider net the many-workgroup MFMA ones."""
+        check(lib.sfx_phi_setup_dims(self._h, int(hid), int(n_mid), float(lr)), "sfx_phi_setup_dims")
+        self.phi_numel = lib.sfx_phi_numel(self._h)
+        self.phi_cfg = dict(hid=int(hid), n_mid=int(n_mid), lr=float(lr))
+
     def phi_load(self, params):
         a = np.ascontiguousarray(torch.as_tensor(params).detach().cpu().reshape(-1).numpy(), dtype=np.float32)
         if a.size != self.phi_numel:
@@ -690,6 +697,26 @@ class SFEngine:
         check(lib.sfx_phi_update(self._h, int(policy), s.data_ptr(), a.data_ptr(), r.data_ptr(), s1.data_ptr(),
                                  gamma.data_ptr(), B, int(bool(use_gpi)), _dev_f32(bias, self.device),
                                  _dev_f32(lam, self.device), losses.data_ptr(), dptr(next_actions)), "sfx_phi_update")
+        return losses
+
+    def tsf_phi_update(self, policy: int, s, a, r, s1, gamma, bias: torch.Tensor, lam: torch.Tensor,
+                       use_gpi: bool = True, losses: Optional[torch.Tensor] = None,
+                       next_actions: Optional[torch.Tensor] = None):
+        """TSFDQN_PHI.update_deep_models (agents/tsfdqn_phi.py:180-288): φ̃ = φ_net(s ⊕ a ⊕ s1) ⊙ (h(g_i(s)) +
+        h(g_i(s1))) with g_i / h the tsf_setup(G = d, K = 0) storage; losses [4] = (loss, psi_loss, phi_loss,
+        λ after the step); bias / lam as phi_update."""
+        s, s1, a, gamma, r = self._h2d_many([(s, torch.float32), (s1, torch.float32), (a, torch.long),
+                                             (gamma, torch.float32), (r, torch.float32)])
+        s, s1 = s.contiguous(), s1.contiguous()
+        B = s.shape[0]
+        a = a.reshape(-1).contiguous()
+        gamma, r = gamma.reshape(B).contiguous(), r.reshape(B).contiguous()
+        if losses is None:
+            losses = torch.empty(4, device=self.device)
+        check(lib.sfx_tsf_phi_update(self._h, int(policy), s.data_ptr(), a.data_ptr(), r.data_ptr(), s1.data_ptr(),
+                                     gamma.data_ptr(), B, int(bool(use_gpi)), _dev_f32(bias, self.device),
+                                     _dev_f32(lam, self.device), losses.data_ptr(), dptr(next_actions)),
+              "sfx_tsf_phi_update")
         return losses
 
     # ---------------------------------------------------------------- TSF test tasks

@@ -546,6 +546,35 @@ int sfx_phi_update(sfx_t h, int policy, const float* S_dev, const int64_t* a_dev
                    const float* S1_dev, const float* gamma_dev, int B, int use_gpi, float* bias_dev, float* lambda_dev,
                    float* losses_dev, int64_t* next_dev);
 
+/* The φ net of main_tsfdqn_phi_torch.py (phi_model_lambda: Linear(2 n_s + 1, 2048) + ReLU,
+ * 3 × (Linear(2048, 2048) + ReLU), Linear(2048, d)) has a hidden width that is no multiple of its
+ * input width: sfx_phi_setup_dims is sfx_phi_setup with the hidden width given directly,
+ * 1 <= hid <= 2048, n_mid + 2 <= 8 (the other limits as sfx_phi_setup).  hid <= 128 runs
+ * sfx_phi_setup's kernels (bit-identical to it when hid = width_mul (2 n_s + 1)); a wider net runs
+ * many-workgroup fp32 MFMA kernels, one launch per layer and pass (csrc/sfx_phiw.h).
+ * sfx_phi_numel / _load / _get / _update work on either. */
+int sfx_phi_setup_dims(sfx_t h, int hid, int n_mid, float lr);
+
+/* TSF-DQN with a learned φ: agents/tsfdqn_phi.py TSFDQN_PHI.update_deep_models (:180-288) over
+ * features/deep_tsf_phi.py DeepSF_TSF_PHI, the library of main_tsfdqn_phi_torch.py.  One call is one
+ * update_deep_models(transitions, phi, policy, λ_policy, use_gpi):
+ *   φ̃_b = phi_net(s_b ⊕ a_b ⊕ s1_b) ⊙ (h(g_i(s_b)) + h(g_i(s1_b))), g_i = Linear(n_s, d) of task i and
+ *   h = Linear(d, d) (:154-160); next actions, targets φ̃ + γ ψ⁻_i(s1)[a'] (they carry φ̃'s gradient) and
+ *   loss = MSE(w_i(φ̃), r) + λ_i MSE(ψ_i(s), merged) as sfx_phi_update; every gradient clamped to
+ *   [-1, 1] (:268-270), then one step of a freshly built Adam (lr of the φ setup, moments zero,
+ *   step 1; :249) on ψ_i, the φ net, g_i, h, w_i and its bias, ascent on λ_i, λ_i clamped to
+ *   [1e-2, 1e6]; target sync as sfx_update.  (The ψ heads' Adam epilogue omits the clamp: under a
+ *   fresh Adam the step lr·g/(|g| + ε) is ±lr to within one ulp for |g| >= 1 clamped or not.)
+ * Needs a φ setup (sfx_phi_setup or sfx_phi_setup_dims) and sfx_tsf_setup(G = d, K = 0, ...): g_i and
+ * h live in that setup's storage (sfx_tsf_load_g / _get_g / _load_h / _get_h; g_t packed W [d][n_s],
+ * b [d], h packed W [d][d], b [d]); their persistent Adam moments are neither read nor written.
+ * Anything else: SFX_E_ARG, the message names the missing setup.
+ * losses_dev [4] = (loss, psi_loss, phi_loss, λ_i after the step), the reference's return order;
+ * bias_dev / lambda_dev / next_dev as sfx_phi_update. */
+int sfx_tsf_phi_update(sfx_t h, int policy, const float* S_dev, const int64_t* a_dev, const float* r_dev,
+                       const float* S1_dev, const float* gamma_dev, int B, int use_gpi, float* bias_dev,
+                       float* lambda_dev, float* losses_dev, int64_t* next_dev);
+
 int sfx_tsf_test_action(sfx_t h, const float* s_dev, const float* w_dev, const float* omega_dev, int64_t* a_dev);
 int sfx_tsf_test_update(sfx_t h, const float* s_dev, const float* s1_dev, const int64_t* a_dev, const int64_t* a1_dev,
                         float r, const float* phi_dev, float* w_dev, float* omega_dev, float* adam_state_dev,
