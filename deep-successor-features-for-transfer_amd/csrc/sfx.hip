@@ -252,6 +252,7 @@ struct sfx_handle {
   int* skip = nullptr;            // [T]: the policy repeats the previous round (BwdArgs::skip)
   unsigned long long* skipc = nullptr;  // [0] policies checked, [1] skipped (rounds >= 1)
   bool skip_rounds = true;        // SFX_SKIP=0: every round recomputes every policy
+  bool bwd_merge = true;          // SFX_BWD_MERGE=0: the layer-1 dX keeps its own backward launch (run_bwd)
   StepOut* dout = nullptr;  // device
   // set by the runner while it captures a step: the final k_ver (with action selection)
   // publishes to pub_res instead of a separate k_publish; pub_folded reports that it did
@@ -765,7 +766,14 @@ int run_bwd(sfx_handle* h, int head0, int nhead, int M, const float* x0, const f
     const LayerGeo& L = h->L[l];
     return 24.0 * ((double)L.N * L.K + L.N) + 4.0 * ((double)M * L.N + (double)M * L.K);
   };
-  for (int l = h->NL - 1; l >= 1; --l) {
+  // Merged last launch: the only reader of the layer-1 dX launch's dZ_0 is the layer-0 dW tile of
+  // the launch after it, and a tile needs just its own 32 columns -- so each layer-0 tile computes
+  // them itself (role_dw<.., MG>) and the two launches become one: dW_2 || dW_1 || layer 0 (|| tail).
+  // Only where it is exact and fits: the many-head callers, one 32-row dX tile per head, the fused
+  // layer-0 tiles (one k-tile), no split-N dX, and a launch before it for the TD target.
+  const bool merge = h->bwd_merge && nhead > 1 && !ex.ride && h->NL >= 3 && M <= 32 && ex.fuse_v0 &&
+                     can_fuse_v0(h, M + (ex.v_xn ? 1 : 0)) && h->L[1].N <= DX_SPLIT_N;
+  for (int l = h->NL - 1; l >= (merge ? 2 : 1); --l) {
     const int li = h->NL - 1 - l;
     A.tdg = fuse && li == 0 ? 1 : 0;
     A.xi_src = A.tdg ? td.xi_src : nullptr;
@@ -811,7 +819,17 @@ int run_bwd(sfx_handle* h, int head0, int nhead, int M, const float* x0, const f
   A.nb = dw_tiles(1);
   A.rc = geo(0);
   A.nc = dw_tiles(0);
-  A.tail = h->NL - 1 == tail_at && need_tail ? 1 : 0;
+  const int last = merge ? h->NL - 2 : h->NL - 1;  // index of this launch
+  A.tail = last == tail_at && need_tail ? 1 : 0;
+  double by_last = nhead * (dw_bytes(1) + dw_bytes(0));
+  if (merge) {
+    A.merge = 1;
+    A.ra = geo(1);
+    A.rd = geo(2);
+    A.nd = dw_tiles(2);
+    // + dX_1's W, dZ_1 and activation reads; dZ_0 is neither written nor read
+    by_last += nhead * (dw_bytes(2) + dx_bytes(1) - 4.0 * M * h->L[1].K - 4.0 * M * h->L[0].N);
+  }
   A.fuse_v0 = ex.fuse_v0 ? 1 : 0;
   A.vM = M + (ex.v_xn ? 1 : 0);
   A.vOff = h->actOff[0];
@@ -822,9 +840,12 @@ int run_bwd(sfx_handle* h, int head0, int nhead, int M, const float* x0, const f
   A.ax = ex.fuse_v0 ? ex.ax : nullptr;
   A.aM = ex.fuse_v0 && ex.ax ? ex.aM : 0;
   A.a_noskip = ex.a_noskip;
-  const int ntile = A.nb + A.nc + A.tail;
-  if (!(ex.ride && nhead == 1 && !A.xcd && ex.ride(h->NL - 1, tail_at, A, ntile, nhead * (dw_bytes(1) + dw_bytes(0)))))
-    launch(h, K_BWD, nhead * (dw_bytes(1) + dw_bytes(0)), h->bf16 ? k_bwd<true> : k_bwd<false>,
+  const int ntile = A.nb + A.nc + A.nd + A.tail;
+  if (merge)  // nhead > 1: the XCD-aware 1-D grid
+    launch(h, K_BWD, by_last, h->bf16 ? k_bwd_mg<true> : k_bwd_mg<false>, dim3(8 * cdiv(nhead, 8) * ntile), dim3(256),
+           h->G, A);
+  else if (!(ex.ride && nhead == 1 && !A.xcd && ex.ride(h->NL - 1, tail_at, A, ntile, by_last)))
+    launch(h, K_BWD, by_last, h->bf16 ? k_bwd<true> : k_bwd<false>,
            A.xcd ? dim3(8 * cdiv(nhead, 8) * ntile) : dim3(ntile, nhead), dim3(256), h->G, A);
   LAUNCHCHK();
   return SFX_OK;
@@ -1489,6 +1510,8 @@ int sfx_create(sfx_t* out, int T, int n_s, int H, int n_hidden, const int* acts,
   h->shard_qa = !(eqa && eqa[0] == '0');
   const char* esk = std::getenv("SFX_SKIP");
   h->skip_rounds = !(esk && esk[0] == '0');
+  const char* ebm = std::getenv("SFX_BWD_MERGE");
+  h->bwd_merge = !(ebm && ebm[0] == '0');
   int off = 0, ptorch = 0;
   for (int l = 0; l < h->NL; ++l) {
     LayerGeo Lr{};

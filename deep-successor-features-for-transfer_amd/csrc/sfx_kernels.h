@@ -1202,7 +1202,10 @@ __global__ __launch_bounds__(256) void k_tdg(Geo G, TdgArgs A) {
 // Layers are walked in a ping-pong (dX of l with dW of l+1) so each launch needs only one
 // dZ.  With fuse_v0 the layer-0 dW tiles also run the post-update forward of layer 0 for
 // the rows of S1 (and s_next) into R_V from the freshly written parameters.
-// blockIdx.x selects the role: [0, na) dX; [na, na+nb) dW rb; [.., +nc) dW rc; then tail.
+// The merged last launch (BwdArgs::merge) folds the layer-1 dX into the layer-0 dW tiles: each
+// computes the 32 columns of dZ_0 it consumes (two dX tiles of layer 1) into LDS, so dZ_0 never
+// goes through memory and dW_2 (role rd) runs beside dW_1 and the layer-0 tiles.
+// blockIdx.x selects the role, longest first: [0, nc) dW rc; then nd dW rd; nb dW rb; na dX; tail.
 // blockIdx.y = head - head0.
 // -------------------------------------------------------------------------------------
 struct RoleGeo {
@@ -1232,6 +1235,8 @@ struct BwdArgs {
   float* dxpart;
   unsigned* dxctr;
   RoleGeo ra, rb, rc;  // dX role (layer la), dW roles (lb, lc)
+  RoleGeo rd;          // merged launch: a second plain dW role (nd tiles)
+  int nd, pad5_;
   AdamHP hp, hpw;
   const float* x0;     // layer-0 input (the minibatch states S)
   const float* phi;    // tail: [M, d]
@@ -1260,7 +1265,8 @@ struct BwdArgs {
   const int64_t* tdg_prev;
   int* skip;
   unsigned long long* skipc;
-  int skip_v0, pad4_;  // skipped heads' layer-0 tiles: 1 = the post-update forward skips them too
+  int skip_v0;         // skipped heads' layer-0 tiles: 1 = the post-update forward skips them too
+  int merge;           // 1: k_bwd_mg -- the rc (layer-0) tiles compute their own dZ_0 = dX of layer ra from dZ_1
   // learned φ (features/deep_phi.py): the output gradient scaled by λ (device scalar)
   const float* dz_scale;
 };
@@ -1453,6 +1459,84 @@ __device__ int tdg_rows(const Geo& G, const BwdArgs& A, int pol, int m0, bool pu
   return 0;
 }
 
+// The accumulate half of a plain dX tile: rows ma / mb of dZ (N columns, [nbeg, nend) of them) times
+// W[n][kk[s]] for NS column sub-tiles that share the dZ row loads; wave w takes the 64-wide chunks
+// w, w + 4, ... and lane group g 16 columns of each, in mfma4's k order (bf16 mode: element j of
+// bf16 step s2 is n = nb + 8 s2 + j, W from the bf16 copy of the read slot).  acc[s][0 / 1]: the
+// wave's partial sums of rows m0.. / m0 + 16.. of sub-tile s; dx_red_sum adds the four waves'.
+// One chunk's operands (dx_load) and its MFMAs (dx_mma) are separate so that a caller can request
+// the operands ahead of other loads.
+template <bool BF, int NS>
+struct DxOps {
+  float a0[16], a1[16];
+  float bw[BF ? 1 : NS][16];
+  bf16x8 w16[BF ? NS : 1][2];
+};
+
+// chunk nc (columns nc + 16 g ..) of the wave; nc >= nend: all zeros
+template <bool C, bool BF, int NS>
+__device__ __forceinline__ void dx_load(DxOps<BF, NS>& o, const float* dZ, const float* W, const __bf16* W16, int N, int K,
+                                        int nc, int nend, int ma, int mb, bool oka, bool okb, const int (&kk)[NS]) {
+  const int nb = nc + ((threadIdx.x & 63) >> 4) * 16;
+  const bool vec = (N & 63) == 0, in = nc < nend;
+  load16u<C>(o.a0, dZ + (size_t)ma * N, nb, nend, oka && in, vec);
+  load16u<C>(o.a1, dZ + (size_t)mb * N, nb, nend, okb && in, vec);
+#pragma unroll
+  for (int s = 0; s < NS; ++s) {
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+      const bool ok = kk[s] < K && nb + j < nend;
+      if constexpr (BF) o.w16[s][j >> 3][j & 7] = ok ? W16[(size_t)(nb + j) * K + kk[s]] : (__bf16)0.f;
+      else o.bw[s][j] = ok ? W[(size_t)(nb + j) * K + kk[s]] : 0.f;
+    }
+  }
+}
+
+template <bool BF, int NS>
+__device__ __forceinline__ void dx_mma(const DxOps<BF, NS>& o, floatx4 (&acc)[NS][2]) {
+  if constexpr (BF) {
+#pragma unroll
+    for (int s2 = 0; s2 < 2; ++s2) {
+      const bf16x8 x0 = to_bf16x8(o.a0 + 8 * s2), x1 = to_bf16x8(o.a1 + 8 * s2);
+#pragma unroll
+      for (int s = 0; s < NS; ++s) {
+        acc[s][0] = mfma_bf16(x0, o.w16[s][s2], acc[s][0]);
+        acc[s][1] = mfma_bf16(x1, o.w16[s][s2], acc[s][1]);
+      }
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+#pragma unroll
+      for (int s = 0; s < NS; ++s) {
+        acc[s][0] = mfma4(o.a0[j], o.bw[s][j], acc[s][0]);
+        acc[s][1] = mfma4(o.a1[j], o.bw[s][j], acc[s][1]);
+      }
+    }
+  }
+}
+
+template <bool C, bool BF, int NS>
+__device__ __forceinline__ void dx_accum(const float* dZ, const float* W, const __bf16* W16, int N, int K, int nbeg,
+                                         int nend, int ma, int mb, bool oka, bool okb, const int (&kk)[NS],
+                                         floatx4 (&acc)[NS][2]) {
+  for (int nc = nbeg + (threadIdx.x >> 6) * 64; nc < nend; nc += 256) {
+    DxOps<BF, NS> o;
+    dx_load<C, BF, NS>(o, dZ, W, W16, N, K, nc, nend, ma, mb, oka, okb, kk);
+    dx_mma<BF, NS>(o, acc);
+  }
+}
+
+// Sum of the four waves' partial tiles in wave order: element (s, Lx) of a dX tile's reduction
+// buffer -- rows 16 s + 4 (Lx >> 4) + i (i = 0..3), column Lx & 15.
+__device__ __forceinline__ floatx4 dx_red_sum(const floatx4 (*red)[2][64], int s, int Lx) {
+  floatx4 v = red[0][s][Lx];
+  v += red[1][s][Lx];
+  v += red[2][s][Lx];
+  v += red[3][s][Lx];
+  return v;
+}
+
 template <bool TDG, int VMAX = 2, int U = 8, bool C = false, bool BF = false>
 __device__ __forceinline__ void role_dx(const Geo& G, const BwdArgs& A, int head, int tile, floatx4 (*red)[2][64]) {
   static_assert(!(BF && (TDG || C)), "bf16 dX: the plain dX tiles only (the fused TD launch stays fp32)");
@@ -1524,36 +1608,12 @@ __device__ __forceinline__ void role_dx(const Geo& G, const BwdArgs& A, int head
       }
     }
   } else {
-    const float* dZ = G.dzp(head, L.dzOff);
-    const bool vec = (N & 63) == 0;
-    for (int nc = nbeg + wave * 64; nc < nend; nc += 256) {
-      const int nb = nc + g * 16;
-      float a0[16], a1[16], bw[16];
-      load16u<C>(a0, dZ + (size_t)ma * N, nb, nend, oka, vec);
-      load16u<C>(a1, dZ + (size_t)mb * N, nb, nend, okb, vec);
-      if constexpr (BF) {
-        // the reduction index n = nb + 8s + j as element j of bf16 step s (a permutation of the
-        // fp32 path's k-steps); W from the bf16 copy of the read slot
-        const __bf16* W16 = G.on16 + G.slot_off(rslot(A.mask, head), head) + L.wOff;
-        bf16x8 w16[2];
-#pragma unroll
-        for (int j = 0; j < 16; ++j)
-          w16[j >> 3][j & 7] = (okk && nb + j < nend) ? W16[(size_t)(nb + j) * K + kk] : (__bf16)0.f;
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2) {
-          acc0 = mfma_bf16(to_bf16x8(a0 + 8 * s2), w16[s2], acc0);
-          acc1 = mfma_bf16(to_bf16x8(a1 + 8 * s2), w16[s2], acc1);
-        }
-        continue;
-      }
-#pragma unroll
-      for (int j = 0; j < 16; ++j) bw[j] = (okk && nb + j < nend) ? W[(size_t)(nb + j) * K + kk] : 0.f;
-#pragma unroll
-      for (int j = 0; j < 16; ++j) {
-        acc0 = mfma4(a0[j], bw[j], acc0);
-        acc1 = mfma4(a1[j], bw[j], acc1);
-      }
-    }
+    const int kks[1] = {kk};
+    floatx4 acc[1][2] = {{acc0, acc1}};
+    dx_accum<C, BF, 1>(G.dzp(head, L.dzOff), W, BF ? G.on16 + G.slot_off(rslot(A.mask, head), head) + L.wOff : nullptr, N, K,
+                       nbeg, nend, ma, mb, oka, okb, kks, acc);
+    acc0 = acc[0][0];
+    acc1 = acc[0][1];
   }
   PROBE_MARK();
   red[wave][0][lane] = acc0;
@@ -1564,10 +1624,7 @@ __device__ __forceinline__ void role_dx(const Geo& G, const BwdArgs& A, int head
     const size_t pt = ((size_t)(head - A.head0) * ntile + tile) * A.dxs;
     __shared__ int s_last;
     if (threadIdx.x < 128) {
-      floatx4 v = red[0][s][Lx];
-      v += red[1][s][Lx];
-      v += red[2][s][Lx];
-      v += red[3][s][Lx];
+      const floatx4 v = dx_red_sum(red, s, Lx);
       float* o = A.dxpart + ((pt + split) * 128 + threadIdx.x) * 4;
 #ifdef SFX_CHECK
       SFX_CHK((long long)((pt + split) * 128 + threadIdx.x) * 4 + 3 < G.ext_dxpart, pt, split, G.ext_dxpart);
@@ -1604,10 +1661,7 @@ __device__ __forceinline__ void role_dx(const Geo& G, const BwdArgs& A, int head
     return;
   }
   if (threadIdx.x < 128) {
-    floatx4 v = red[0][s][Lx];
-    v += red[1][s][Lx];
-    v += red[2][s][Lx];
-    v += red[3][s][Lx];
+    const floatx4 v = dx_red_sum(red, s, Lx);
     if (col < K) {
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
@@ -1774,8 +1828,14 @@ __device__ __forceinline__ void role_v0_only(const Geo& G, const BwdArgs& A, int
   fused_v0<false>(G, A, L, head, nbase, sW, sB, sX, sm.sWt, sm.sBt, vrows);
 }
 
-template <bool C = false, bool BF = false>
-__device__ __forceinline__ void role_dw(const Geo& G, const BwdArgs& A, int head, const RoleGeo& L, int tile, bool fuse) {
+// MG (layer-0 tiles of the merged launch; M <= 32, one k-tile, no split N): dZ of this tile's 32
+// columns is not read from memory but computed here, as the two dX tiles of layer A.ra at columns
+// nbase and nbase + 16 -- role_dx<false>'s arithmetic (dx_accum, dx_red_sum, act_bwd), so the
+// same bits -- whose per-wave partial sums meet in red / red2; every lane then sums the four
+// waves' partials of the eight dZ elements its dW MFMAs take.
+template <bool C = false, bool BF = false, bool MG = false>
+__device__ __forceinline__ void role_dw(const Geo& G, const BwdArgs& A, int head, const RoleGeo& L, int tile, bool fuse,
+                                        floatx4 (*red)[2][64] = nullptr) {
   const int N = L.N, K = L.K, M = A.M;
   const int ntk = (K + 63) >> 6;
   const int kt = tile % ntk, nt = tile / ntk;
@@ -1853,12 +1913,59 @@ __device__ __forceinline__ void role_dw(const Geo& G, const BwdArgs& A, int head
   __builtin_amdgcn_sched_barrier(0);  // keep those loads ahead of the MFMA operands
   floatx4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
   float bsum = 0.f;
+  float dz0[MT / 4], xb0[MT / 4], xb1[MT / 4];  // MG: dZ[4 j + g][nn] and the rows' dW operands
+  if constexpr (MG) {
+    static_assert(MT == 32, "merged tile: the 32 rows of one dX tile are the one row chunk of dW");
+    __shared__ floatx4 red2[4][2][64];
+    // every load of the tile is requested before the first wait: the dX operands (this wave's
+    // chunks of dZ_1 and W_1; layer 0's output for act_bwd) and the dW operands of layer 0 after
+    // the Adam state and the forward's rows above.  (The dX operands first, or in a batch of
+    // their own that is waited for before the rest is requested, measured slower: AB_LOG.md.)
+    const RoleGeo& L1 = A.ra;
+    const float* Y0 = layer_input(G, A, head, L1.xOff);
+    float y0[MT / 4];
+#pragma unroll
+    for (int j = 0; j < MT / 4; ++j) {
+      const int m = 4 * j + g;
+      y0[j] = (m < M && nn < N) ? Y0[(size_t)m * N + nn] : 0.f;
+      xb0[j] = (m < M && kb0 < K) ? X[(size_t)m * K + kb0] : 0.f;
+      xb1[j] = (m < M && kb1 < K) ? X[(size_t)m * K + kb1] : 0.f;
+    }
+    const int kks[2] = {nbase + r, nbase + 16 + r};
+    floatx4 dacc[2][2] = {};
+    dx_accum<false, BF, 2>(G.dzp(head, L1.dzOff), Pr + L1.wOff, BF ? G.on16 + ro + L1.wOff : nullptr, L1.N, L1.K, 0, L1.N, r,
+                           16 + r, r < M, 16 + r < M, kks, dacc);
+    red[wave][0][lane] = dacc[0][0];
+    red[wave][1][lane] = dacc[0][1];
+    red2[wave][0][lane] = dacc[1][0];
+    red2[wave][1][lane] = dacc[1][1];
+    PROBE_AT(6);
+    __syncthreads();
+    // row 4 j + g, column (wave & 1) * 16 + r: element g of entry (s = j >> 2, Lx = (j & 3) * 16 + r)
+    const floatx4 (*rd)[2][64] = (wave & 1) ? red2 : red;
+#pragma unroll
+    for (int j = 0; j < MT / 4; ++j) {
+      const int s = j >> 2, Lx = (j & 3) * 16 + r;
+      float v = rd[0][s][Lx][g];
+      v = __fadd_rn(v, rd[1][s][Lx][g]);
+      v = __fadd_rn(v, rd[2][s][Lx][g]);
+      v = __fadd_rn(v, rd[3][s][Lx][g]);
+      dz0[j] = (4 * j + g < M && nn < N) ? act_bwd(v, y0[j], L1.actIn) : 0.f;
+    }
+    PROBE_AT(7);
+  }
   for (int mc = 0; mc < M; mc += MT) {
     float av[MT / 4], bv0[MT / 4], bv1[MT / 4];
 #pragma unroll
     for (int j = 0; j < MT / 4; ++j) {
       const int m = mc + 4 * j + g;
       const bool okm = m < M;
+      if constexpr (MG) {
+        av[j] = dz0[j];
+        bv0[j] = xb0[j];
+        bv1[j] = xb1[j];
+        continue;
+      }
       av[j] = (okm && nn < N) ? ldc<C>(dZ + (size_t)m * N + nn) : 0.f;
       bv0[j] = (okm && kb0 < K) ? X[(size_t)m * K + kb0] : 0.f;
       bv1[j] = (okm && kb1 < K) ? X[(size_t)m * K + kb1] : 0.f;
@@ -2004,7 +2111,8 @@ __device__ __forceinline__ void role_tail(const Geo& G, const BwdArgs& A, int he
 }
 
 // tile bx of head `head` of a backward launch (k_bwd; k_bwd_tsf after its TSF blocks)
-template <bool BF>
+// MG: the merged last launch (k_bwd_mg), whose layer-0 tiles compute their own dZ_0
+template <bool BF, bool MG = false>
 __device__ __forceinline__ void bwd_body(const Geo& G, const BwdArgs& A, int head, int bx, floatx4 (*red)[2][64]) {
   PROBE_T(pt0);
   PROBE_MARKA();
@@ -2016,11 +2124,18 @@ __device__ __forceinline__ void bwd_body(const Geo& G, const BwdArgs& A, int hea
       if (A.fuse_v0 && (!A.skip_v0 || (A.aM > 0 && A.a_noskip))) role_v0_only(G, A, head, A.rc, bx, !A.skip_v0);
       return;
     }
-    role_dw<false, BF>(G, A, head, A.rc, bx, A.fuse_v0 != 0);
+    role_dw<false, BF, MG>(G, A, head, A.rc, bx, A.fuse_v0 != 0, red);
     PROBE_REC(6, pt0);
     return;
   }
   bx -= A.nc;
+  if (bx < A.nd) {
+    if (skip) return;
+    role_dw<false, BF>(G, A, head, A.rd, bx, false);
+    PROBE_REC(5, pt0);
+    return;
+  }
+  bx -= A.nd;
   if (bx < A.nb) {
     if (skip) return;
     role_dw<false, BF>(G, A, head, A.rb, bx, false);
@@ -2042,10 +2157,21 @@ __global__ __launch_bounds__(256) void k_bwd(Geo G, BwdArgs A) {
   __shared__ floatx4 red[4][2][64];
   int head = A.head0 + blockIdx.y, bx = blockIdx.x;
   if (A.xcd) {
-    if (!xcd_decode(blockIdx.x, A.nhead, A.na + A.nb + A.nc + A.tail, head, bx)) return;
+    if (!xcd_decode(blockIdx.x, A.nhead, A.na + A.nb + A.nc + A.nd + A.tail, head, bx)) return;
     head += A.head0;
   }
   bwd_body<BF>(G, A, head, bx, red);
+}
+
+// The merged last launch of the many-head callers (run_bwd): dW rc with its own dX || dW rd || dW rb
+// (|| tail); always an XCD-aware 1-D grid.  A kernel of its own: its layer-0 tiles hold more
+// registers and LDS than k_bwd's, which the other backward launches then do not pay for.
+template <bool BF = false>
+__global__ __launch_bounds__(256) void k_bwd_mg(Geo G, BwdArgs A) {
+  __shared__ floatx4 red[4][2][64];
+  int head, bx;
+  if (!xcd_decode(blockIdx.x, A.nhead, A.na + A.nb + A.nc + A.nd + A.tail, head, bx)) return;
+  bwd_body<BF, true>(G, A, head + A.head0, bx, red);
 }
 
 // First backward launch with K2 fused: dX of the last layer only (A.na tiles per head).
