@@ -39,6 +39,7 @@
 #include "sfx_phi.h"
 #include "sfx_phiw.h"
 #include "sfx_tsfphi.h"
+#include "sfx_phitest.h"
 #include "../../include/sfx.h"
 
 using namespace sfx;

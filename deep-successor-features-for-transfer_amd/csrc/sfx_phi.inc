@@ -160,14 +160,16 @@ PhiwLayer phiw_layer(sfx_handle* h, int l, int B, int clamp) {
   return A;
 }
 
-int phiw_forward(sfx_handle* h, int B, const float* S, const int64_t* a, const float* S1) {
+// out: where the last layer's φ [B][d] goes (nullptr: the state's phis)
+int phiw_forward(sfx_handle* h, int B, const float* S, const int64_t* a, const float* S1, float* out = nullptr) {
   sfx_phi_state* s = h->phi;
   const int L = s->n_mid + 2, MT = cdiv(B, 16);
   launch(h, K_TSF, 4.0 * 2.0 * B * s->n_in, k_phiw_in, dim3(cdiv(B * s->n_in, 256)), dim3(256),
          s->acts + (size_t)(L - 1) * B * s->hid, S, a, S1, B, h->n_s);
   LAUNCHCHK();
   for (int l = 0; l < L; ++l) {
-    const PhiwLayer A = phiw_layer(h, l, B, 0);
+    PhiwLayer A = phiw_layer(h, l, B, 0);
+    if (out && l == L - 1) A.Y = out;
     const double bytes = 4.0 * ((double)A.N * (A.K + 1) + (double)B * (A.K + A.N));
     const dim3 grid(cdiv(A.N, 16));
     switch (MT) {
@@ -335,6 +337,161 @@ int sfx_tsf_phi_update(sfx_t h, int policy, const float* S, const int64_t* a, co
   if (!valid_head(h, policy) || B < 1 || B > h->Mmax || !S || !a || !r || !S1 || !gamma || !bias || !lambda || !losses)
     SFX_FAIL(SFX_E_ARG, "bad args");
   return phi_update_impl(h, 31, 1, policy, S, a, r, S1, gamma, B, use_gpi, bias, lambda, losses, next);
+}
+
+}  // extern "C"
+
+// ---- the learned-φ agents' test phase (kernels and the math: sfx_phitest.h) ------------------
+
+namespace {
+
+// what every test-phase call needs: an unsharded handle and a φ setup; the TSF ones also g_t / h as plain
+// Linears (sfx_tsf_setup(G = d, K = 0)) and shapes one workgroup of k_tsfphi_test_* holds
+int phi_test_ok(sfx_handle* h, bool tsf, const char* name) {
+  if (!h) SFX_FAIL(SFX_E_ARG, std::string(name) + ": null handle");
+  if (h->Tg != h->T) SFX_FAIL(SFX_E_ARG, std::string(name) + ": needs an unsharded handle");
+  if (!h->phi) SFX_FAIL(SFX_E_ARG, std::string(name) + ": call sfx_phi_setup or sfx_phi_setup_dims first");
+  if (!tsf) return SFX_OK;
+  if (!h->tsf) SFX_FAIL(SFX_E_ARG, std::string(name) + ": call sfx_tsf_setup(G = d, K = 0) first");
+  if (h->tsf->G != h->d || h->tsf->K != 0)
+    SFX_FAIL(SFX_E_ARG, std::string(name) + ": needs sfx_tsf_setup with G = d and K = 0 (g_i, h plain Linear)");
+  const long long Td = (long long)h->T * h->d;
+  if (h->d > PHIT_D || h->A > PHIT_A || h->A * h->d > PHIT_AD || Td > PHIT_TD || h->A * Td > PHIT_ATD)
+    SFX_FAIL(SFX_E_ARG, std::string(name) + ": needs d <= 64, A <= 64, A d <= 1024, T d <= 1024, A T d <= 4096");
+  return SFX_OK;
+}
+
+// φ of B rows into out [B][d]: one row of a wide net through the one-row kernels, anything else through the
+// update's forward
+int phi_features_impl(sfx_handle* h, const float* S, const int64_t* a, const float* S1, int B, float* out) {
+  sfx_phi_state* s = h->phi;
+  if (!s->wide) {
+    PhiArgs A = phi_args(h, 0, B);
+    A.S = S;
+    A.S1 = S1;
+    A.a = a;
+    A.phis = out;
+    launch(h, K_TSF, 4.0 * (s->P + (double)B * (s->n_in + (s->n_mid + 1.0) * s->hid + h->d)), k_phi_fwd, dim3(1),
+           dim3(256), A);
+    LAUNCHCHK();
+    return SFX_OK;
+  }
+  if (B > 1) {
+    RC(phi_lazy_buffers(h, false));
+    return phiw_forward(h, B, S, a, S1, out);
+  }
+  const int L = s->n_mid + 2;
+  size_t off = 0;
+  for (int l = 0; l < L; ++l) {
+    Phi1Args A{};
+    A.K = l == 0 ? s->n_in : s->hid;
+    A.N = l == L - 1 ? h->d : s->hid;
+    A.W = s->p + off;
+    off += (size_t)A.N * (A.K + 1);
+    A.X = l == 0 ? nullptr : s->acts + (size_t)(l - 1) * s->hid;
+    A.Y = l == L - 1 ? out : s->acts + (size_t)l * s->hid;
+    A.s = S;
+    A.s1 = S1;
+    A.a = a;
+    A.n_s = h->n_s;
+    A.relu = l < L - 1;
+    launch(h, K_TSF, 4.0 * ((double)A.N * (A.K + 2) + A.K), k_phi1_fwd, dim3(cdiv(A.N, PHI1_R)),
+           dim3(64 * PHI1_R * PHI1_S), A);
+    LAUNCHCHK();
+  }
+  return SFX_OK;
+}
+
+PhiTestArgs phi_test_args(sfx_handle* h) {
+  PhiTestArgs A{};
+  A.T = h->T;
+  A.A = h->A;
+  A.d = h->d;
+  A.n_s = h->n_s;
+  A.lastOff = h->actOff[h->NL - 1];
+  A.actSize = h->actSize;
+  A.phi = h->phi->phis;
+  A.hpa = AdamHP{h->phi->lr, 0.0, h->hp_psi.b1, h->hp_psi.b2, h->hp_psi.eps};
+  return A;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sfx_phi_features(sfx_t h, const float* S, const int64_t* a, const float* S1, int B, float* phi) {
+  RC(settle(h));
+  RC(phi_test_ok(h, false, "sfx_phi_features"));
+  if (!S || !a || !S1 || !phi) SFX_FAIL(SFX_E_ARG, "sfx_phi_features: null argument");
+  if (B < 1 || B > h->Mmax) SFX_FAIL(SFX_E_ARG, "sfx_phi_features: B must be in [1, max_batch]");
+  return phi_features_impl(h, S, a, S1, B, phi);
+}
+
+int sfx_tsf_phi_test_action(sfx_t h, const float* s, const float* omega_w, const float* omega_b, const float* w,
+                            const float* wb, int64_t* a_out) {
+  RC(settle(h));
+  RC(phi_test_ok(h, true, "sfx_tsf_phi_test_action"));
+  if (!s || !omega_w || !omega_b || !w || !wb || !a_out) SFX_FAIL(SFX_E_ARG, "sfx_tsf_phi_test_action: null argument");
+  RC(run_fwd(h, {{R_A, P_ONLINE, 1, 0, h->T}}, 1, s, nullptr));
+  PhiTestArgs A = phi_test_args(h);
+  A.psi = h->act + (size_t)R_A * h->T * h->actSize;
+  A.oW = const_cast<float*>(omega_w);
+  A.ob = const_cast<float*>(omega_b);
+  A.w = const_cast<float*>(w);
+  A.wb = const_cast<float*>(wb);
+  A.act_out = a_out;
+  launch(h, K_GPI, 4.0 * ((double)h->T * h->O + (double)h->d * (h->T * h->d + 2.0)), k_tsfphi_test_act, dim3(1),
+         dim3(256), A);
+  LAUNCHCHK();
+  return SFX_OK;
+}
+
+int sfx_tsf_phi_test_update(sfx_t h, const float* s, const int64_t* a, float r, const float* s1, float gamma,
+                            float* omega_w, float* omega_b, float* w, float* wb, float* lambda, float* losses) {
+  RC(settle(h));
+  RC(phi_test_ok(h, true, "sfx_tsf_phi_test_update"));
+  if (!s || !a || !s1 || !omega_w || !omega_b || !w || !wb || !lambda || !losses)
+    SFX_FAIL(SFX_E_ARG, "sfx_tsf_phi_test_update: null argument");
+  sfx_tsf_state* ts = h->tsf;
+  RC(phi_features_impl(h, s, a, s1, 1, h->phi->phis));
+  // ψ_t(s) of the online heads and ψ⁻_t(s1) of the target heads, one forward for both
+  RC(run_fwd(h, {{R_A, P_ONLINE, 1, 0, h->T}, {R_G, P_TARGET, 2, 0, h->T}}, 1, s, s1));
+  PhiTestArgs A = phi_test_args(h);
+  A.psi = h->act + (size_t)R_A * h->T * h->actSize;
+  A.psi1 = h->act + (size_t)R_G * h->T * h->actSize;
+  A.s = s;
+  A.s1 = s1;
+  A.g = ts->g;
+  A.Pg = ts->Pg;
+  A.hp = ts->hp;
+  A.oW = omega_w;
+  A.ob = omega_b;
+  A.w = w;
+  A.wb = wb;
+  A.lam = lambda;
+  A.r = r;
+  A.gamma = gamma;
+  A.losses = losses;
+  launch(h, K_TSF, 4.0 * (2.0 * h->T * h->O + (double)h->T * ts->Pg + ts->Ph + 2.0 * h->d * (h->T * h->d + 2.0)),
+         k_tsfphi_test_step, dim3(1), dim3(256), A);
+  LAUNCHCHK();
+  return SFX_OK;
+}
+
+int sfx_phi_test_update(sfx_t h, const float* s, const int64_t* a, float r, const float* s1, float* w, float* wb,
+                        float* loss) {
+  RC(settle(h));
+  RC(phi_test_ok(h, false, "sfx_phi_test_update"));
+  if (!s || !a || !s1 || !w || !wb || !loss) SFX_FAIL(SFX_E_ARG, "sfx_phi_test_update: null argument");
+  RC(phi_features_impl(h, s, a, s1, 1, h->phi->phis));
+  PhiTestArgs A = phi_test_args(h);
+  A.w = w;
+  A.wb = wb;
+  A.r = r;
+  A.losses = loss;
+  launch(h, K_TSF, 4.0 * 3.0 * h->d, k_phi_test_step, dim3(1), dim3(64), A);
+  LAUNCHCHK();
+  return SFX_OK;
 }
 
 }  // extern "C"

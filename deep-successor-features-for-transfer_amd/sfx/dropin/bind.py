@@ -10,9 +10,13 @@ test-task methods get_test_action / update_test_reward_mapper (tsfdqn.py:859-997
 rank 1) become libsfx calls too (DeepTSF.tsf_test_action / tsf_test_update), drawing from
 Python's random module exactly where the reference does.  ``agents.tsfdqn_phi``'s
 ``TSFDQN_PHI.update_deep_models`` (:180-288, TSF-DQN with a learned φ) becomes one libsfx call
-(DeepSF_TSF_PHI.tsf_phi_update); its test phase stays the agent's own torch code, run after the
-device's φ net, g_i and h are copied back into the agent's modules.  Nothing else of the user's
-agents is touched.
+(DeepSF_TSF_PHI.tsf_phi_update), and its test phase's get_test_action / update_target_models
+(:381-397, :434-505) become libsfx calls on the agent's own ``omegas``, the test task's reward model
+and loss coefficient (DeepSF_TSF_PHI.tsf_phi_test_action / tsf_phi_test_update);
+``agents.sfdqn_phi``'s update_test_reward_mapper (:263-305) likewise (DeepSF_PHI.phi_test_update).
+Where the agent's modules are not the shapes the library runs, those methods fall back to the
+agent's own torch code, after the device's φ net, g_i and h are copied back into its modules -- as
+``test_agent`` is wrapped to do once per test episode.  Nothing else of the user's agents is touched.
 """
 from __future__ import annotations
 
@@ -168,6 +172,63 @@ def _tsf_phi_synced(method):
     return run
 
 
+def _fallback(self, sync_name):
+    """Before the agent's own torch code runs: the device's state into its modules, if an update ran since."""
+    sync = getattr(self.sf, sync_name, None)
+    if sync is not None:
+        self.sf.sync_if_stale(sync)
+
+
+def bind_tsf_phi_test(cls) -> None:
+    """TSFDQN_PHI.get_test_action (agents/tsfdqn_phi.py:381-397) and update_target_models (:434-505) as
+    library calls; the agent's own methods where its modules are not the library's shapes (``omegas`` not an
+    nn.Linear(T d, d) with bias, a w_approx without bias, tensors off the engine's device, a φ net the setups
+    refuse).  The ε draw is the reference's: random.random(), then random.randrange, from Python's random."""
+    own_action, own_update = cls.get_test_action, cls.update_target_models
+    if getattr(own_action, "__sfx_bound__", False):
+        return
+
+    @functools.wraps(own_action)
+    def get_test_action(self, s_enc, w):
+        if not self.sf.tsf_phi_test_supported(self, w):
+            _fallback(self, "sync_tsf_phi_modules")
+            return own_action(self, s_enc, w)
+        with torch.no_grad():
+            if random.random() <= self.test_epsilon:
+                return torch.tensor(random.randrange(self.n_actions)).to(self.device)
+            return self.sf.tsf_phi_test_action(self, s_enc, w)
+
+    @functools.wraps(own_update)
+    def update_target_models(self, w_approx, target_loss_coefficient, r, s_enc, a, s1_enc):
+        if not self.sf.tsf_phi_test_supported(self, w_approx, target_loss_coefficient):
+            _fallback(self, "sync_tsf_phi_modules")
+            return own_update(self, w_approx, target_loss_coefficient, r, s_enc, a, s1_enc)
+        return self.sf.tsf_phi_test_update(self, w_approx, target_loss_coefficient, r, s_enc, a, s1_enc)
+
+    get_test_action.__sfx_bound__ = update_target_models.__sfx_bound__ = True
+    cls.get_test_action, cls.update_target_models = get_test_action, update_target_models
+
+
+def bind_phi_test(cls) -> None:
+    """SFDQN_PHI.update_test_reward_mapper (agents/sfdqn_phi.py:263-305) as one library call; the agent's own
+    method where w_approx is not an nn.Linear(d, 1) with bias on the engine's device or the setups refuse the
+    φ net.  get_test_action already goes through GPI_w."""
+    own = cls.update_test_reward_mapper
+    if getattr(own, "__sfx_bound__", False):
+        return
+
+    @functools.wraps(own)
+    def update_test_reward_mapper(self, w_approx, r, s_enc, a, s1_enc):
+        phi_model = self.phi[0][0]
+        if not self.sf.phi_test_supported(phi_model, w_approx):
+            _fallback(self, "sync_phi_module")
+            return own(self, w_approx, r, s_enc, a, s1_enc)
+        return self.sf.phi_test_update(phi_model, w_approx, r, s_enc, a, s1_enc)
+
+    update_test_reward_mapper.__sfx_bound__ = True
+    cls.update_test_reward_mapper = update_test_reward_mapper
+
+
 def patch(name: str, module) -> None:
     """Bind the user's freshly loaded module ``name`` to sfx (see the module docstring)."""
     if name == "sfdqn":
@@ -181,6 +242,8 @@ def patch(name: str, module) -> None:
         m = getattr(module.SFDQN_PHI, "test_agent", None)
         if m is not None and not getattr(m, "__sfx_bound__", False):
             module.SFDQN_PHI.test_agent = _phi_synced(m)
+        if hasattr(module.SFDQN_PHI, "update_test_reward_mapper"):
+            bind_phi_test(module.SFDQN_PHI)
     elif name == "agents.tsfdqn_phi":
         cls = getattr(module, "TSFDQN_PHI", None)
         if cls is None:  # not the reference's module: nothing to bind
@@ -189,3 +252,5 @@ def patch(name: str, module) -> None:
         m = getattr(cls, "test_agent", None)
         if m is not None and not getattr(m, "__sfx_bound__", False):
             cls.test_agent = _tsf_phi_synced(m)
+        if hasattr(cls, "get_test_action") and hasattr(cls, "update_target_models"):
+            bind_tsf_phi_test(cls)

@@ -10,7 +10,10 @@ on ψ_i, φ, w_i (lr 1e-3, as the reference hard-codes) and ascent on λ_i, clam
 The agent's loss coefficient and each reward model's bias are updated in place when they live on
 the engine's device (staged through it otherwise).
 ``sync_phi_module`` copies the device's φ into the agent's module (sfx.dropin.bind calls it before
-the agent's test episodes, which run the φ net in torch).
+the agent's test episodes).  The test phase's reward mapper (agents/sfdqn_phi.py:263-305,
+update_test_reward_mapper) is ``phi_test_update``: φ of the one transition through the engine's φ net
+(loaded from the agent's module if no update has done so yet) and one fresh Adam step on the test
+task's own nn.Linear(d, 1), in place (sfx_phi_test_update).
 """
 from __future__ import annotations
 
@@ -45,6 +48,19 @@ def _phi_geometry(model: torch.nn.Module, n_s: int, d: int):
     return hid, len(lin) - 2, (hid // n_in if hid % n_in == 0 and hid <= PHI_NARROW else None)
 
 
+PHI_WIDE, PHI_LAYERS, PHI_IN = 2048, 8, 64  # sfx_phi_setup_dims' limits (sfx_phiw.h PHIW_HID, sfx_phi.h PHI_L, PHI_IN)
+
+
+def _on_engine_device(t, dev) -> bool:
+    return (torch.is_tensor(t) and t.device == dev and t.dtype == torch.float32 and t.is_contiguous())
+
+
+def _is_linear(m, n_in: int, n_out: int, dev) -> bool:
+    """m is an nn.Linear(n_in, n_out) WITH bias whose tensors the device can update in place."""
+    return (isinstance(m, torch.nn.Linear) and m.bias is not None and (m.in_features, m.out_features) == (n_in, n_out)
+            and _on_engine_device(m.weight, dev) and _on_engine_device(m.bias, dev))
+
+
 class _FitWBias(list):
     """fit_w entries: nn.Linear(d, 1) with bias.  The engine owns the weight rows once it exists
     (refreshed on read); the bias stays in the module's own tensor, which the device updates in
@@ -73,6 +89,8 @@ class DeepSF_PHI(_deep.DeepSF):
         super().reset()
         self.fit_w = _FitWBias(self)
         self._phi_model = self._phi_eng = None
+        self._phi_updates = self._phi_synced_at = 0  # updates run / at the last copy into the agent's modules
+        self._phi_fits_cache = {}
 
     def add_training_task(self, task, source=None):
         """features/deep_phi.py:254-285: the ψ networks first, then a biased Linear(d, 1)."""
@@ -123,6 +141,46 @@ class DeepSF_PHI(_deep.DeepSF):
         if self._phi_ready():
             _unflat_into(self._phi_model, self._eng.phi_get())
 
+    def sync_if_stale(self, sync):
+        """Run ``sync`` (one of the sync_* methods) unless it ran since the last update: the fallback of a
+        rebound test-phase method runs the agent's torch code per step, the modules change per update."""
+        if self._phi_synced_at != self._phi_updates:
+            sync()
+            self._phi_synced_at = self._phi_updates
+
+    # ------------------------------------------------------------------ test phase
+    def _phi_fits(self, phi_model) -> bool:
+        """The φ setups take this net (the shapes of _phi_geometry within sfx_phi_setup_dims' limits)."""
+        known = self._phi_fits_cache.get(id(phi_model))
+        if known is not None and known[0] is phi_model:
+            return known[1]
+        try:
+            hid, n_mid, _ = _phi_geometry(phi_model, self.inputs, self.n_features)
+            ok = (hid <= PHI_WIDE and n_mid + 2 <= PHI_LAYERS and 2 * self.inputs + 1 <= PHI_IN
+                  and self.n_features <= PHI_IN)
+        except NotImplementedError:
+            ok = False
+        ok = ok and (self._phi_model is None or phi_model is self._phi_model)
+        self._phi_fits_cache[id(phi_model)] = (phi_model, ok)
+        return ok
+
+    def _test_device(self):
+        return self._eng.device if self._eng is not None else torch.device("cuda", torch.cuda.current_device())
+
+    def phi_test_supported(self, phi_model, w_approx) -> bool:
+        """sfx_phi_test_update can run this step: w_approx an nn.Linear(d, 1) with bias on the engine's
+        device, a φ net the setups take.  Pure Python: no library call."""
+        return (self.n_tasks > 0 and _is_linear(w_approx, self.n_features, 1, self._test_device())
+                and self._phi_fits(phi_model))
+
+    def phi_test_update(self, phi_model, w_approx, r, s_enc, a, s1_enc):
+        """agents/sfdqn_phi.py:263-305 update_test_reward_mapper -> the loss (0-dim, as MSELoss returns it);
+        w_approx.weight / .bias updated in place."""
+        eng = self._phi_engine(phi_model, 1)
+        self._flush()
+        loss = eng.phi_test_update(s_enc, a, float(r), s1_enc, w_approx.weight.data, w_approx.bias.data)
+        return loss.reshape(()).to(self._out_device())
+
     # ------------------------------------------------------------------ GPI with the biased w
     def GPI_w(self, state, w):
         s = self._state(state)
@@ -158,6 +216,7 @@ class DeepSF_PHI(_deep.DeepSF):
         bias, bias_staged = self._dev_scalar(bias_mod.data, eng)
         lam, lam_staged = self._dev_scalar(loss_coefficient.data, eng)
         losses = eng.phi_update(policy_index, states, actions, rs, next_states, gammas, bias, lam, use_gpi=use_gpi)
+        self._phi_updates += 1
         with torch.no_grad():
             if bias_staged:
                 bias_mod.copy_(bias.view_as(bias_mod))

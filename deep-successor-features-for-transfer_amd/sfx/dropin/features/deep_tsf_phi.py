@@ -11,15 +11,23 @@ reference hard-codes) on Ïˆ_i, the Ï† net, g_i, h, w_i and its bias, ascent on Î
 The agent's Ï† net (main_tsfdqn_phi_torch.py's phi_model_lambda: hidden width 2048, the wide kernels of
 csrc/sfx_phiw.h), the task's g_i and the shared h are loaded into the engine the first time an update
 hands them in, and train there; ``sync_tsf_phi_modules`` copies them back into the agent's modules
-(sfx.dropin.bind calls it before the agent's test episodes, which run them in torch over this class's
-``get_successors`` / ``get_next_successors``).
+(sfx.dropin.bind calls it before the agent's test episodes).
+
+The test phase (agents/tsfdqn_phi.py:381-505) runs in the library too: ``tsf_phi_test_action`` is
+get_test_action's greedy branch (sfx_tsf_phi_test_action), ``tsf_phi_test_update`` is update_target_models
+(sfx_tsf_phi_test_update) on the agent's own ``omegas``, the test task's nn.Linear(d, 1) and its loss
+coefficient, all three updated in place.  A test step may come before the first training update: it loads
+the agent's Ï† net, h and EVERY g_t the engine has not seen yet.
 """
 from __future__ import annotations
 
 import torch
 
 from .deep import _flat, _unflat_into
-from .deep_phi import LR, DeepSF_PHI
+from .deep_phi import LR, DeepSF_PHI, _is_linear, _on_engine_device
+
+# one workgroup of k_tsfphi_test_* (csrc/sfx_phitest.h): d, A, A d, T d, A T d
+TEST_LIMITS = (64, 64, 1024, 1024, 4096)
 
 
 class DeepSF_TSF_PHI(DeepSF_PHI):
@@ -81,6 +89,7 @@ class DeepSF_TSF_PHI(DeepSF_PHI):
         lam, lam_staged = self._dev_scalar(loss_coefficient.data, eng)
         losses = eng.tsf_phi_update(policy_index, states, actions, rs, next_states, gammas, bias, lam,
                                     use_gpi=use_gpi)
+        self._phi_updates += 1
         with torch.no_grad():
             if bias_staged:
                 bias_mod.copy_(bias.view_as(bias_mod))
@@ -100,3 +109,53 @@ class DeepSF_TSF_PHI(DeepSF_PHI):
             _unflat_into(g, self._eng.tsf_get_g(t)[0])
         if self._h_mod is not None:
             _unflat_into(self._h_mod, self._eng.tsf_get_h())
+
+    # ------------------------------------------------------------------ test phase
+    def tsf_phi_test_supported(self, agent, w_approx, lam=None) -> bool:
+        """The library can run this agent's test step: ``omegas`` an nn.Linear(T d, d) and w_approx an
+        nn.Linear(d, 1), both with bias and on the engine's device, Î» a one-element float32 tensor there, g_t
+        and h plain Linears, a Ï† net the setups take, shapes within k_tsfphi_test_*'s.  Pure Python: no
+        library call.  ``omegas`` is read from the agent each time: add_training_task re-creates it."""
+        T, d, A, dev = self.n_tasks, self.n_features, self.n_actions, self._test_device()
+        if T == 0 or d > TEST_LIMITS[0] or A > TEST_LIMITS[1] or A * d > TEST_LIMITS[2] or T * d > TEST_LIMITS[3] \
+                or A * T * d > TEST_LIMITS[4]:
+            return False
+        gs, h = getattr(agent, "g_functions", None), getattr(agent, "h_function", None)
+        ok = _is_linear(getattr(agent, "omegas", None), T * d, d, dev) and _is_linear(w_approx, d, 1, dev)
+        ok = ok and (lam is None or (_on_engine_device(lam, dev) and lam.numel() == 1))
+        ok = ok and isinstance(h, torch.nn.Linear) and h.bias is not None and (h.in_features, h.out_features) == (d, d)
+        ok = ok and gs is not None and len(gs) == T and all(
+            isinstance(g, torch.nn.Linear) and g.bias is not None and (g.in_features, g.out_features) == (self.inputs, d)
+            for g in gs)
+        return bool(ok) and self._phi_fits(agent.phi[0][0])
+
+    def _tsf_phi_test_engine(self, agent):
+        """The engine with the agent's Ï† net, h and every g_t loaded (those no update has handed in yet)."""
+        pm, gs, h = agent.phi[0][0], agent.g_functions, agent.h_function
+        if self._phi_model is pm and self._h_mod is h and len(self._g_mods) == len(gs) and \
+                all(self._g_mods.get(t) is g for t, g in enumerate(gs)):
+            return self._phi_engine(pm, 1)
+        eng = None
+        for t, g in enumerate(gs):
+            eng = self._tsf_phi_engine(pm, g, h, t, 1)
+        return eng
+
+    def tsf_phi_test_action(self, agent, s_enc, w_approx):
+        """agents/tsfdqn_phi.py:381-397, the greedy branch -> a 0-dim int64 tensor."""
+        eng = self._tsf_phi_test_engine(agent)
+        self._flush()
+        om = agent.omegas
+        a = eng.tsf_phi_test_action(torch.as_tensor(s_enc).reshape(-1), om.weight.data, om.bias.data,
+                                    w_approx.weight.data, w_approx.bias.data)
+        return a.to(self._out_device())
+
+    def tsf_phi_test_update(self, agent, w_approx, lam, r, s_enc, a, s1_enc):
+        """agents/tsfdqn_phi.py:434-505 update_target_models -> (loss [1], psi_loss, phi_loss); ``agent.omegas``,
+        w_approx and Î» updated in place."""
+        eng = self._tsf_phi_test_engine(agent)
+        self._flush()
+        om = agent.omegas
+        lo = eng.tsf_phi_test_update(s_enc, a, float(r), s1_enc, float(agent.gamma), om.weight.data, om.bias.data,
+                                     w_approx.weight.data, w_approx.bias.data, lam.data)
+        dev = self._out_device()
+        return lo[0:1].to(dev), lo[1].to(dev), lo[2].to(dev)

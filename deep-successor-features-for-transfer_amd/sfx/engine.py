@@ -719,6 +719,61 @@ class SFEngine:
               "sfx_tsf_phi_update")
         return losses
 
+    # ---------------------------------------------------------------- learned φ: the agents' test phase
+    def phi_features(self, s, a, s1, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """φ = phi_net(s ⊕ a ⊕ s1), forward only: s, s1 [B, n_s] (or [n_s]), a [B] -> [B, d].  One row of a
+        wide net (hid > 128) runs the one-row GEMV kernels, anything else the update's forward."""
+        s, s1, a = self._h2d_many([(s, torch.float32), (s1, torch.float32), (a, torch.long)])
+        s, s1 = s.reshape(-1, self.n_s).contiguous(), s1.reshape(-1, self.n_s).contiguous()
+        a = a.reshape(-1).contiguous()
+        B = s.shape[0]
+        if s1.shape[0] != B or a.numel() != B:
+            raise ValueError("phi_features: s, a and s1 must have the same number of rows")
+        out = torch.empty(B, self.d, device=self.device) if out is None else out
+        check(lib.sfx_phi_features(self._h, s.data_ptr(), a.data_ptr(), s1.data_ptr(), B,
+                                   _dev_f32(out, self.device)), "sfx_phi_features")
+        return out
+
+    def tsf_phi_test_action(self, s, omega_w: torch.Tensor, omega_b: torch.Tensor, w: torch.Tensor,
+                            wb: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """TSFDQN_PHI.get_test_action's greedy branch (agents/tsfdqn_phi.py:381-397): a 0-d int64 device
+        tensor.  omega_w [d, T d] / omega_b [d] (the agent's `omegas`), w [d] / wb [1] (the test task's
+        Linear(d, 1)) are float32 device tensors, read in place."""
+        s = self._f(s, (-1,))
+        out = torch.empty((), dtype=torch.long, device=self.device) if out is None else out
+        check(lib.sfx_tsf_phi_test_action(self._h, s.data_ptr(), _dev_f32(omega_w, self.device),
+                                          _dev_f32(omega_b, self.device), _dev_f32(w, self.device),
+                                          _dev_f32(wb, self.device), out.data_ptr()), "sfx_tsf_phi_test_action")
+        return out
+
+    def tsf_phi_test_update(self, s, a, r: float, s1, gamma: float, omega_w: torch.Tensor, omega_b: torch.Tensor,
+                            w: torch.Tensor, wb: torch.Tensor, lam: torch.Tensor,
+                            losses: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """TSFDQN_PHI.update_target_models (agents/tsfdqn_phi.py:434-505): updates omega_w, omega_b, w, wb and
+        lam (float32 device tensors) in place; returns losses [3] = (loss, psi_loss, phi_loss)."""
+        s, s1, a = (t.reshape(-1).contiguous() for t in self._h2d_many(
+            [(s, torch.float32), (s1, torch.float32), (a, torch.long)]))
+        if losses is None:
+            losses = torch.empty(3, device=self.device)
+        check(lib.sfx_tsf_phi_test_update(self._h, s.data_ptr(), a.data_ptr(), float(r), s1.data_ptr(), float(gamma),
+                                          _dev_f32(omega_w, self.device), _dev_f32(omega_b, self.device),
+                                          _dev_f32(w, self.device), _dev_f32(wb, self.device),
+                                          _dev_f32(lam, self.device), losses.data_ptr()), "sfx_tsf_phi_test_update")
+        return losses
+
+    def phi_test_update(self, s, a, r: float, s1, w: torch.Tensor, wb: torch.Tensor,
+                        loss: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """SFDQN_PHI.update_test_reward_mapper (agents/sfdqn_phi.py:263-305): updates w [d] and wb [1] in
+        place; returns the loss, a one-element device tensor."""
+        s, s1, a = (t.reshape(-1).contiguous() for t in self._h2d_many(
+            [(s, torch.float32), (s1, torch.float32), (a, torch.long)]))
+        if loss is None:
+            loss = torch.empty(1, device=self.device)
+        check(lib.sfx_phi_test_update(self._h, s.data_ptr(), a.data_ptr(), float(r), s1.data_ptr(),
+                                      _dev_f32(w, self.device), _dev_f32(wb, self.device), loss.data_ptr()),
+              "sfx_phi_test_update")
+        return loss
+
     # ---------------------------------------------------------------- TSF test tasks
     def tsf_test_action(self, s, w: torch.Tensor, omega: torch.Tensor, out: Optional[torch.Tensor] = None):
         """TSFDQN.get_test_action's greedy branch (tsfdqn.py:859-870): a 0-d int64 device tensor.

@@ -575,6 +575,36 @@ int sfx_tsf_phi_update(sfx_t h, int policy, const float* S_dev, const int64_t* a
                        const float* S1_dev, const float* gamma_dev, int B, int use_gpi, float* bias_dev,
                        float* lambda_dev, float* losses_dev, int64_t* next_dev);
 
+/* The learned-φ agents' test phase (kernels and the math: csrc/sfx_phitest.h).  Every call sees the heads, the
+ * φ net, g_t and h as the last training update left them; needs an unsharded handle and a φ setup, the TSF
+ * ones also sfx_tsf_setup(G = d, K = 0) with EVERY g_t loaded, d <= 64, A <= 64, A d <= 1024, T d <= 1024,
+ * A T d <= 4096.  Anything else: SFX_E_ARG, the message names what is missing.  Ω (omega_w_dev [d][T d],
+ * omega_b_dev [d]: the agent's nn.Linear(T d, d) `omegas`), the test task's reward model (w_dev [d], wb_dev
+ * [1]: nn.Linear(d, 1) with bias) and its loss coefficient lambda_dev [1] are caller-owned device tensors,
+ * updated in place; the optimiser is a freshly built Adam (no moment storage) at the φ setup's lr.
+ *
+ * sfx_phi_features: phi_dev [B][d] = phi_net(S ⊕ a ⊕ S1), forward only, 1 <= B <= max_batch.  B = 1 on a
+ *   wide net (hid > 128) runs one-row GEMV kernels, one launch per layer; any other case the update's forward.
+ * sfx_tsf_phi_test_action: TSFDQN_PHI.get_test_action's greedy branch (agents/tsfdqn_phi.py:381-397):
+ *   a_out_dev [1] = argmax_a w(Ω(flat(ψ(s))[a])), flat(ψ)[a][t d + k] = ψ_t[a][k] (first index on ties).
+ * sfx_tsf_phi_test_update: TSFDQN_PHI.update_target_models(w, λ, r, s, a, s1) (agents/tsfdqn_phi.py:434-505):
+ *   φ̃ = phi_net(s ⊕ a ⊕ s1) ⊙ (h(Ω(concat_t g_t(s))) + h(Ω(concat_t g_t(s1)))),
+ *   psi_loss = MSE(Ω(flat(ψ(s))), φ̃ + γ Ω(flat(ψ⁻(s1)))) over the A actions, phi_loss = (w(φ̃) - r)²,
+ *   loss = phi_loss + λ psi_loss (λ before its step); gradients clamped to ±1e10, one fresh Adam step:
+ *   descent on w, its bias and Ω, ascent on λ, λ clamped to [1e-2, 1e6].  ψ, ψ⁻, g_t, h and the φ net are not
+ *   trained.  losses_dev [3] = (loss, psi_loss, phi_loss), the reference's return order.
+ * sfx_phi_test_update: SFDQN_PHI.update_test_reward_mapper(w, r, s, a, s1) (agents/sfdqn_phi.py:263-305):
+ *   loss_dev [1] = (w(phi_net(s ⊕ a ⊕ s1)) - r)², the same clamp, one fresh Adam step on w and its bias.
+ * a_dev: a device int64 scalar (the agent's action tensor). */
+int sfx_phi_features(sfx_t h, const float* S_dev, const int64_t* a_dev, const float* S1_dev, int B, float* phi_dev);
+int sfx_tsf_phi_test_action(sfx_t h, const float* s_dev, const float* omega_w_dev, const float* omega_b_dev,
+                            const float* w_dev, const float* wb_dev, int64_t* a_out_dev);
+int sfx_tsf_phi_test_update(sfx_t h, const float* s_dev, const int64_t* a_dev, float r, const float* s1_dev,
+                            float gamma, float* omega_w_dev, float* omega_b_dev, float* w_dev, float* wb_dev,
+                            float* lambda_dev, float* losses_dev);
+int sfx_phi_test_update(sfx_t h, const float* s_dev, const int64_t* a_dev, float r, const float* s1_dev, float* w_dev,
+                        float* wb_dev, float* loss_dev);
+
 int sfx_tsf_test_action(sfx_t h, const float* s_dev, const float* w_dev, const float* omega_dev, int64_t* a_dev);
 int sfx_tsf_test_update(sfx_t h, const float* s_dev, const float* s1_dev, const int64_t* a_dev, const int64_t* a1_dev,
                         float r, const float* phi_dev, float* w_dev, float* omega_dev, float* adam_state_dev,
