@@ -768,8 +768,9 @@ int run_bwd(sfx_handle* h, int head0, int nhead, int M, const float* x0, const f
     return 24.0 * ((double)L.N * L.K + L.N) + 4.0 * ((double)M * L.N + (double)M * L.K);
   };
   // Merged last launch: the only reader of the layer-1 dX launch's dZ_0 is the layer-0 dW tile of
-  // the launch after it, and a tile needs just its own 32 columns -- so each layer-0 tile computes
-  // them itself (role_dw<.., MG>) and the two launches become one: dW_2 || dW_1 || layer 0 (|| tail).
+  // the launch after it, and a tile needs just its own columns -- so each layer-0 tile (16 columns
+  // wide here) computes them itself (role_dw<.., MG>) and the two launches become one: dW_2 || dW_1
+  // || layer 0 (|| tail).
   // Only where it is exact and fits: the many-head callers, one 32-row dX tile per head, the fused
   // layer-0 tiles (one k-tile), no split-N dX, and a launch before it for the TD target.
   const bool merge = h->bwd_merge && nhead > 1 && !ex.ride && h->NL >= 3 && M <= 32 && ex.fuse_v0 &&
@@ -825,6 +826,7 @@ int run_bwd(sfx_handle* h, int head0, int nhead, int M, const float* x0, const f
   double by_last = nhead * (dw_bytes(1) + dw_bytes(0));
   if (merge) {
     A.merge = 1;
+    A.nc = cdiv(h->L[0].N, 16);  // k_bwd_mg's layer-0 tiles are 16 columns wide (one k-tile: can_fuse_v0)
     A.ra = geo(1);
     A.rd = geo(2);
     A.nd = dw_tiles(2);

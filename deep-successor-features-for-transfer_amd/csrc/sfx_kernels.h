@@ -1679,6 +1679,8 @@ __device__ __forceinline__ void role_dx(const Geo& G, const BwdArgs& A, int head
 // (input rows staged in LDS by role_dw: sX[m * K + k], m < vM); with look-ahead rows also
 // (sX[aoff + m * K + k], m < 2 aM) those rows into R_NS / R_NS1 and, with the target weights sWt,
 // NS1 into R_NS1T.  vrows = false: the look-ahead rows only (a skipped head).
+// NW: the tile's column width -- 32 (k_bwd), or 16 (k_bwd_mg), where all four waves split the
+// 16-row tiles of the one column group.
 __device__ __forceinline__ int v0_aoff(const BwdArgs& A, int K) { return (A.vM * K + 3) & ~3; }
 constexpr int V0S = KFUSE + 4;  // LDS row stride of the tile's weights: lane (r, g) hits bank 4r + g
 
@@ -1716,7 +1718,7 @@ __device__ __forceinline__ void v0_tile(const float* x, int K, int m0, int rows,
   }
 }
 
-template <bool C>
+template <bool C, int NW = 32>
 __device__ __forceinline__ void fused_v0(const Geo& G, const BwdArgs& A, const RoleGeo& L, int head, int nbase, const float* sW,
                          const float* sB, const float* sX, const float* sWt = nullptr, const float* sBt = nullptr,
                          bool vrows = true, bool landed = false) {
@@ -1725,13 +1727,17 @@ __device__ __forceinline__ void fused_v0(const Geo& G, const BwdArgs& A, const R
   __syncthreads();
   PROBE_AT(3);
   const int K = L.K, N = L.N, VM = A.vM;
-  // wave w owns column half (w & 1) and row tiles (w >> 1), (w >> 1) + 2, ...
+  // NW = 32: wave w owns column half (w & 1) and row tiles (w >> 1), (w >> 1) + 2, ...
+  // NW = 16: wave w owns row tiles w, w + 4, ...
+  static_assert(NW == 16 || NW == 32, "layer-0 tile width");
+  constexpr int WS = NW == 32 ? 2 : 4;  // waves that share a column group's row tiles
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, r = lane & 15;
-  const int nl = (wave & 1) * 16 + r, n = nbase + nl;
+  const int wt = NW == 32 ? wave >> 1 : wave;
+  const int nl = (NW == 32 ? (wave & 1) * 16 : 0) + r, n = nbase + nl;
   const float bias = sB[nl];
   if (vrows) {
     float* Y = G.actp(A.vRole, head, A.vOff);
-    for (int mt = wave >> 1; mt * 16 < VM; mt += 2)
+    for (int mt = wt; mt * 16 < VM; mt += WS)
       v0_tile<C>(sX, K, mt * 16, VM, sW + nl * V0S, bias, A.act0, Y, N, n, G.actSize - A.vOff);
   }
   PROBE_AT(4);
@@ -1741,7 +1747,7 @@ __device__ __forceinline__ void fused_v0(const Geo& G, const BwdArgs& A, const R
     const int aM = A.aM, nt = (aM + 15) >> 4;
     const float* xa = sX + v0_aoff(A, K);
     const float bt = sBt[nl];
-    for (int it = wave >> 1; it < 3 * nt; it += 2) {
+    for (int it = wt; it < 3 * nt; it += WS) {
       const int which = it / nt, mt = it - which * nt;
       v0_tile<C>(xa + (which ? aM * K : 0), K, mt * 16, aM, which == 2 ? sWt + nl * K : sW + nl * V0S,
                  which == 2 ? bt : bias, A.act0, G.actp(which == 0 ? R_NS : which == 1 ? R_NS1 : R_NS1T, head, A.vOff),
@@ -1774,73 +1780,83 @@ __device__ __forceinline__ void glds(float* dst, int n, F src, int w0 = 0, int n
 
 // LDS of the fused post-update layer-0 forward, one instance per kernel for both of its callers
 // (role_dw's layer-0 tiles and role_v0_only): the tile's weights and biases, the input rows, the
-// target weights and biases of the look-ahead rows.
+// target weights and biases of the look-ahead rows.  NW: the tile's column width.
+template <int NW = 32>
 struct V0Smem {
-  float sW[32 * V0S];
-  float sB[32];
-  float sWt[32 * KFUSE];
-  float sBt[32];
+  float sW[NW * V0S];
+  float sB[NW];
+  float sWt[NW * KFUSE];
+  float sBt[NW];
   __align__(16) float sX[VFUSE];
 };
-__device__ __forceinline__ V0Smem& v0_smem() {
-  __shared__ V0Smem sm;
+template <int NW = 32>
+__device__ __forceinline__ V0Smem<NW>& v0_smem() {
+  __shared__ V0Smem<NW> sm;
   return sm;
 }
 
 // The look-ahead operands by LDS-DMA (no registers; they land while the tile does its dW): the
-// 2 aM input rows (BwdArgs::ax) at sX + v0_aoff, the target weights of columns [nbase, nbase + 32)
-// (32 contiguous rows of K floats; row stride K in sWt) and their biases.  Landed at fused_v0.
+// 2 aM input rows (BwdArgs::ax) at sX + v0_aoff, the target weights of columns [nbase, nbase + NW)
+// (NW contiguous rows of K floats; row stride K in sWt) and their biases.  Landed at fused_v0.
+template <int NW>
 __device__ __forceinline__ void v0_stage_ahead(const Geo& G, const BwdArgs& A, const RoleGeo& L, int head, int nbase,
-                                               V0Smem& sm) {
-  const int K = L.K, ncol = L.N - nbase < 32 ? L.N - nbase : 32;
+                                               V0Smem<NW>& sm) {
+  const int K = L.K, ncol = L.N - nbase < NW ? L.N - nbase : NW;
   const float* ax = A.ax;
   glds(sm.sX + v0_aoff(A, K), 2 * A.aM * K, [&](int j) -> const float* { return ax + j; });
   const float* Pt = G.target + (long long)head * G.P;
   const float* tw = Pt + L.wOff + (size_t)nbase * K;
-  glds(sm.sWt, 32 * K, [&](int j) -> const float* { return j < ncol * K ? tw + j : nullptr; });
+  glds(sm.sWt, NW * K, [&](int j) -> const float* { return j < ncol * K ? tw + j : nullptr; });
   const float* tb = Pt + L.bOff + nbase;
-  glds(sm.sBt, 32, [&](int j) -> const float* { return j < ncol ? tb + j : nullptr; }, 0, 1);
+  glds(sm.sBt, NW, [&](int j) -> const float* { return j < ncol ? tb + j : nullptr; }, 0, 1);
 }
 
 // A layer-0 dW tile of a policy that repeats the previous round (BwdArgs::skip): no gradient,
 // no Adam -- the write slot already holds this round's weights -- only the fused post-update
-// forward of its 32 columns, from those weights (the bits role_dw would have staged): every row
+// forward of its NW columns, from those weights (the bits role_dw would have staged): every row
 // (vrows), or the look-ahead rows alone (BwdArgs::a_noskip).
-// Fused layers have K <= KFUSE <= 64: one k-tile, so tile = column tile.
+// Fused layers have K <= KFUSE <= 64: one k-tile, so tile = column tile (of the launch's width NW:
+// a skipped head's tiles share the tile index space of role_dw's).
+template <int NW = 32>
 __device__ __forceinline__ void role_v0_only(const Geo& G, const BwdArgs& A, int head, const RoleGeo& L, int tile, bool vrows) {
-  const int N = L.N, K = L.K, M = A.M, tid = threadIdx.x, nbase = tile * 32;
+  const int N = L.N, K = L.K, M = A.M, tid = threadIdx.x, nbase = tile * NW;
   const float* Pw = G.online + G.slot_off(rslot(A.mask, head) ^ 1, head);
-  V0Smem& sm = v0_smem();
+  V0Smem<NW>& sm = v0_smem<NW>();
   float* sW = sm.sW;
   float* sB = sm.sB;
   float* sX = sm.sX;
   if (A.aM > 0) v0_stage_ahead(G, A, L, head, nbase, sm);
   const FDiv fK = fdiv(K);
-  for (int j = tid; j < 32 * K; j += 256) {
+  for (int j = tid; j < NW * K; j += 256) {
     const int nl = j / fK, k = j - nl * K;
     sW[nl * V0S + k] = nbase + nl < N ? Pw[L.wOff + (size_t)(nbase + nl) * K + k] : 0.f;
   }
-  if (tid < 32) sB[tid] = nbase + tid < N ? Pw[L.bOff + nbase + tid] : 0.f;
+  if (tid < NW) sB[tid] = nbase + tid < N ? Pw[L.bOff + nbase + tid] : 0.f;
   if (vrows) {
     const int nxs = A.vM * K;
     for (int j = tid; j < nxs; j += 256) sX[j] = j < M * K ? A.v_x[j] : A.v_xn[j - M * K];
   }
-  fused_v0<false>(G, A, L, head, nbase, sW, sB, sX, sm.sWt, sm.sBt, vrows);
+  fused_v0<false, NW>(G, A, L, head, nbase, sW, sB, sX, sm.sWt, sm.sBt, vrows);
 }
 
-// MG (layer-0 tiles of the merged launch; M <= 32, one k-tile, no split N): dZ of this tile's 32
-// columns is not read from memory but computed here, as the two dX tiles of layer A.ra at columns
-// nbase and nbase + 16 -- role_dx<false>'s arithmetic (dx_accum, dx_red_sum, act_bwd), so the
-// same bits -- whose per-wave partial sums meet in red / red2; every lane then sums the four
-// waves' partials of the eight dZ elements its dW MFMAs take.
+// MG (layer-0 tiles of the merged launch; M <= 32, one k-tile, no split N): a tile is 16 columns
+// wide, not 32 (twice the workgroups, each pulling half of W_1 through its CU), and its dZ is not
+// read from memory but computed here, as the dX tile of layer A.ra at columns nbase.. --
+// role_dx<false>'s arithmetic (dx_accum, dx_red_sum's wave order, act_bwd), so the same bits --
+// whose per-wave partial sums meet in red; every lane then sums the four waves' partials of the
+// eight dZ elements its dW MFMAs take.  Wave w takes the one 16-wide k group 16 w.. of the dW
+// block (each dW element is one MFMA chain over the rows, whichever wave runs it).
 template <bool C = false, bool BF = false, bool MG = false>
 __device__ __forceinline__ void role_dw(const Geo& G, const BwdArgs& A, int head, const RoleGeo& L, int tile, bool fuse,
                                         floatx4 (*red)[2][64] = nullptr) {
+  constexpr int NW = MG ? 16 : 32;  // tile width
+  constexpr int NH = MG ? 1 : 2;    // 16-wide k groups per wave (kb0, kb1)
   const int N = L.N, K = L.K, M = A.M;
   const int ntk = (K + 63) >> 6;
   const int kt = tile % ntk, nt = tile / ntk;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, r = lane & 15, g = lane >> 4;
-  const int nbase = nt * 32, n0 = nbase + (wave & 1) * 16, k0 = kt * 64 + (wave >> 1) * 32;
+  const int nbase = nt * NW, n0 = MG ? nbase : nbase + (wave & 1) * 16;
+  const int k0 = kt * 64 + (MG ? wave * 16 : (wave >> 1) * 32);
   const float* dZ = G.dzp(head, L.dzOff);
   const float* X = layer_input(G, A, head, L.xOff);
   const int rs = rslot(A.mask, head);
@@ -1854,16 +1870,16 @@ __device__ __forceinline__ void role_dw(const Geo& G, const BwdArgs& A, int head
   const AdamC c = load_adamc<C>(G.adamc + head);  // bias corrections of this step (double pow once per head)
   const int cx = step_cancelled(G.cancel);
   const int nn = n0 + r, kb0 = k0 + r, kb1 = k0 + 16 + r;
-  // prefetch the optimizer state of the 8 weights this lane will update
-  float pp[8], pm[8], pv[8];
-  bool ok[8];
+  // prefetch the optimizer state of the 8 (MG: 4) weights this lane will update
+  float pp[4 * NH], pm[4 * NH], pv[4 * NH];
+  bool ok[4 * NH];
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int n = n0 + g * 4 + i;
 #pragma unroll
-    for (int h = 0; h < 2; ++h) {
+    for (int h = 0; h < NH; ++h) {
       const int k = h ? kb1 : kb0;
-      const int e = i * 2 + h;
+      const int e = i * NH + h;
       ok[e] = n < N && k < K;
       const size_t off = (size_t)L.wOff + (size_t)n * K + k;
       pp[e] = ok[e] ? Pr[off] : 0.f;
@@ -1874,7 +1890,8 @@ __device__ __forceinline__ void role_dw(const Geo& G, const BwdArgs& A, int head
   // bias of column n0 + r: lane r of waves 0/1 (k-half 0) of the kt == 0 tiles.  Its gradient
   // Σ_m dZ[m][n] comes from the dZ operands already in registers (no extra loads: a lane
   // stays under the 63 outstanding loads the vmcnt counter tracks).
-  const bool dob = kt == 0 && wave < 2 && g == 0 && nn < N;
+  // (MG: lane r of wave 0 -- every wave holds the one column group's dZ)
+  const bool dob = kt == 0 && wave < (MG ? 1 : 2) && g == 0 && nn < N;
   const int nbias = nn;
   float bp = 0.f, bm = 0.f, bv = 0.f;
   if (dob) {
@@ -1890,7 +1907,7 @@ __device__ __forceinline__ void role_dw(const Geo& G, const BwdArgs& A, int head
   float xn = 0.f;
   const int nx = fuse ? M * K : 0;
   const int nxn = fuse && A.v_xn ? K : 0;
-  if (fuse && A.aM > 0) v0_stage_ahead(G, A, L, head, nbase, v0_smem());
+  if (fuse && A.aM > 0) v0_stage_ahead(G, A, L, head, nbase, v0_smem<NW>());
   if (fuse) {
     if ((nx & 3) == 0 && (reinterpret_cast<uintptr_t>(A.v_x) & 15) == 0) {
 #pragma unroll
@@ -1913,10 +1930,9 @@ __device__ __forceinline__ void role_dw(const Geo& G, const BwdArgs& A, int head
   __builtin_amdgcn_sched_barrier(0);  // keep those loads ahead of the MFMA operands
   floatx4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
   float bsum = 0.f;
-  float dz0[MT / 4], xb0[MT / 4], xb1[MT / 4];  // MG: dZ[4 j + g][nn] and the rows' dW operands
+  float dz0[MT / 4], xb0[MT / 4];  // MG: dZ[4 j + g][nn] and the rows' dW operand
   if constexpr (MG) {
     static_assert(MT == 32, "merged tile: the 32 rows of one dX tile are the one row chunk of dW");
-    __shared__ floatx4 red2[4][2][64];
     // every load of the tile is requested before the first wait: the dX operands (this wave's
     // chunks of dZ_1 and W_1; layer 0's output for act_bwd) and the dW operands of layer 0 after
     // the Adam state and the forward's rows above.  (The dX operands first, or in a batch of
@@ -1929,27 +1945,23 @@ __device__ __forceinline__ void role_dw(const Geo& G, const BwdArgs& A, int head
       const int m = 4 * j + g;
       y0[j] = (m < M && nn < N) ? Y0[(size_t)m * N + nn] : 0.f;
       xb0[j] = (m < M && kb0 < K) ? X[(size_t)m * K + kb0] : 0.f;
-      xb1[j] = (m < M && kb1 < K) ? X[(size_t)m * K + kb1] : 0.f;
     }
-    const int kks[2] = {nbase + r, nbase + 16 + r};
-    floatx4 dacc[2][2] = {};
-    dx_accum<false, BF, 2>(G.dzp(head, L1.dzOff), Pr + L1.wOff, BF ? G.on16 + ro + L1.wOff : nullptr, L1.N, L1.K, 0, L1.N, r,
+    const int kks[1] = {nbase + r};
+    floatx4 dacc[1][2] = {};
+    dx_accum<false, BF, 1>(G.dzp(head, L1.dzOff), Pr + L1.wOff, BF ? G.on16 + ro + L1.wOff : nullptr, L1.N, L1.K, 0, L1.N, r,
                            16 + r, r < M, 16 + r < M, kks, dacc);
     red[wave][0][lane] = dacc[0][0];
     red[wave][1][lane] = dacc[0][1];
-    red2[wave][0][lane] = dacc[1][0];
-    red2[wave][1][lane] = dacc[1][1];
     PROBE_AT(6);
     __syncthreads();
-    // row 4 j + g, column (wave & 1) * 16 + r: element g of entry (s = j >> 2, Lx = (j & 3) * 16 + r)
-    const floatx4 (*rd)[2][64] = (wave & 1) ? red2 : red;
+    // row 4 j + g, column r: element g of entry (s = j >> 2, Lx = (j & 3) * 16 + r)
 #pragma unroll
     for (int j = 0; j < MT / 4; ++j) {
       const int s = j >> 2, Lx = (j & 3) * 16 + r;
-      float v = rd[0][s][Lx][g];
-      v = __fadd_rn(v, rd[1][s][Lx][g]);
-      v = __fadd_rn(v, rd[2][s][Lx][g]);
-      v = __fadd_rn(v, rd[3][s][Lx][g]);
+      float v = red[0][s][Lx][g];
+      v = __fadd_rn(v, red[1][s][Lx][g]);
+      v = __fadd_rn(v, red[2][s][Lx][g]);
+      v = __fadd_rn(v, red[3][s][Lx][g]);
       dz0[j] = (4 * j + g < M && nn < N) ? act_bwd(v, y0[j], L1.actIn) : 0.f;
     }
     PROBE_AT(7);
@@ -1963,7 +1975,6 @@ __device__ __forceinline__ void role_dw(const Geo& G, const BwdArgs& A, int head
       if constexpr (MG) {
         av[j] = dz0[j];
         bv0[j] = xb0[j];
-        bv1[j] = xb1[j];
         continue;
       }
       av[j] = (okm && nn < N) ? ldc<C>(dZ + (size_t)m * N + nn) : 0.f;
@@ -1973,7 +1984,7 @@ __device__ __forceinline__ void role_dw(const Geo& G, const BwdArgs& A, int head
 #pragma unroll
     for (int j = 0; j < MT / 4; ++j) {
       acc0 = mfma4(av[j], bv0[j], acc0);
-      acc1 = mfma4(av[j], bv1[j], acc1);
+      if constexpr (!MG) acc1 = mfma4(av[j], bv1[j], acc1);
     }
 #pragma unroll
     for (int j = 0; j < MT / 4; ++j) bsum = __fadd_rn(bsum, av[j]);  // rows mc + 4j + g
@@ -1985,7 +1996,7 @@ __device__ __forceinline__ void role_dw(const Geo& G, const BwdArgs& A, int head
   // wait after them (in fused_v0) would also wait for every store to drain
   if (fuse && A.aM > 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   PROBE_MARK();
-  V0Smem& sm = v0_smem();
+  V0Smem<NW>& sm = v0_smem<NW>();
   float* sW = sm.sW;
   float* sB = sm.sB;
   float* sX = sm.sX;
@@ -2007,8 +2018,8 @@ __device__ __forceinline__ void role_dw(const Geo& G, const BwdArgs& A, int head
   for (int i = 0; i < 4; ++i) {
     const int n = n0 + g * 4 + i;
 #pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const int e = i * 2 + h;
+    for (int h = 0; h < NH; ++h) {
+      const int e = i * NH + h;
       if (ok[e]) {
         const int k = h ? kb1 : kb0;
         const size_t off = (size_t)L.wOff + (size_t)n * K + k;
@@ -2036,7 +2047,7 @@ __device__ __forceinline__ void role_dw(const Geo& G, const BwdArgs& A, int head
     }
     if (fuse) sB[nbias - nbase] = bp;
   }
-  if (fuse) fused_v0<C>(G, A, L, head, nbase, sW, sB, sX, sm.sWt, sm.sBt, true, true);
+  if (fuse) fused_v0<C, NW>(G, A, L, head, nbase, sW, sB, sX, sm.sWt, sm.sBt, true, true);
 }
 
 // loss finalisation, optional w step, Adam step counter (one workgroup per head)
@@ -2121,7 +2132,7 @@ __device__ __forceinline__ void bwd_body(const Geo& G, const BwdArgs& A, int hea
   // bulk of the launch does: layer-0 dW (+ the fused post-update forward), dW, dX, tail
   if (bx < A.nc) {
     if (skip) {
-      if (A.fuse_v0 && (!A.skip_v0 || (A.aM > 0 && A.a_noskip))) role_v0_only(G, A, head, A.rc, bx, !A.skip_v0);
+      if (A.fuse_v0 && (!A.skip_v0 || (A.aM > 0 && A.a_noskip))) role_v0_only<MG ? 16 : 32>(G, A, head, A.rc, bx, !A.skip_v0);
       return;
     }
     role_dw<false, BF, MG>(G, A, head, A.rc, bx, A.fuse_v0 != 0, red);
@@ -2164,8 +2175,8 @@ __global__ __launch_bounds__(256) void k_bwd(Geo G, BwdArgs A) {
 }
 
 // The merged last launch of the many-head callers (run_bwd): dW rc with its own dX || dW rd || dW rb
-// (|| tail); always an XCD-aware 1-D grid.  A kernel of its own: its layer-0 tiles hold more
-// registers and LDS than k_bwd's, which the other backward launches then do not pay for.
+// (|| tail); always an XCD-aware 1-D grid.  A kernel of its own: its layer-0 tiles are 16 columns
+// wide and hold more registers than k_bwd's, which the other backward launches then do not pay for.
 template <bool BF = false>
 __global__ __launch_bounds__(256) void k_bwd_mg(Geo G, BwdArgs A) {
   __shared__ floatx4 red[4][2][64];
