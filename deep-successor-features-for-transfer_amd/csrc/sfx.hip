@@ -436,7 +436,7 @@ struct FwdExtra {
   const int* skip = nullptr;  // post-update forward of rounds r >= 1 (FwdArgs::skip; one group)
   int* qh = nullptr;          // sharded rounds: the local heads' maxima terms (FwdArgs::qh)
   int* qhs = nullptr;
-  // the first launch when it is the fused layer-0+1 one (k_fwd<true, 8, true, BF, TP>): issued by
+  // the first launch when it is the fused layer-0+1 one (k_fwd<true, true, BF, TP>): issued by
   // the caller instead, with workgroups of its own riding along (TSF: k_fwd_tsf); returns true when
   // it launched
   std::function<bool(const FwdArgs& F, dim3 grid, double bytes)> ride_l0;
@@ -492,7 +492,7 @@ int run_fwd(sfx_handle* h, std::initializer_list<FwdGroup> groups, int M, const 
     F.flag = first ? ex.flag : nullptr;
     F.flag_value = ex.flag_value;
     const bool qa = ex.qa_role >= 0 && l == h->NL - 1;  // the maxima come from the ψ output layer
-    // the vector path needs K % (256/NW) == 0 and 16-B aligned rows of X (layer 0 reads the caller's S)
+    // the vector path needs K % (256 / FWD_WAVES) == 0 and 16-B aligned rows of X (layer 0 reads the caller's S)
     const bool aligned = l > 0 || ((uintptr_t)xa % 16 == 0 && (uintptr_t)xb % 16 == 0);
     bool own = false;  // groups with their own rows on an XCD grid: per-group row tiles (FwdArgs::rowsplit)
     if (F.xcd)
@@ -564,16 +564,16 @@ int run_fwd(sfx_handle* h, std::initializer_list<FwdGroup> groups, int M, const 
     } else if (l0) {
       if (!(ex.ride_l0 && !F.xcd && ex.ride_l0(F, grid, by)))
         launch(h, K_FWD, by,
-               tp2 ? (h->bf16 ? k_fwd<true, 8, true, true, 2> : k_fwd<true, 8, true, false, 2>)
-                   : (h->bf16 ? k_fwd<true, 8, true, true> : k_fwd<true, 8, true>),
-               grid, dim3(512), h->G, F);
+               tp2 ? (h->bf16 ? k_fwd<true, true, true, 2> : k_fwd<true, true, false, 2>)
+                   : (h->bf16 ? k_fwd<true, true, true> : k_fwd<true, true>),
+               grid, dim3(64 * FWD_WAVES), h->G, F);
     } else {  // (the tpw rule above requires the vector path)
       const bool vec = (L.K % 32) == 0 && aligned;
       launch(h, K_FWD, by,
-             !vec ? k_fwd<false, 8, false>
-                  : tp2 ? (h->bf16 ? k_fwd<true, 8, false, true, 2> : k_fwd<true, 8, false, false, 2>)
-                        : (h->bf16 ? k_fwd<true, 8, false, true> : k_fwd<true, 8, false>),
-             grid, dim3(512), h->G, F);
+             !vec ? k_fwd<false, false>
+                  : tp2 ? (h->bf16 ? k_fwd<true, false, true, 2> : k_fwd<true, false, false, 2>)
+                        : (h->bf16 ? k_fwd<true, false, true> : k_fwd<true, false>),
+             grid, dim3(64 * FWD_WAVES), h->G, F);
     }
   }
   LAUNCHCHK();
@@ -703,9 +703,23 @@ int run_bwd(sfx_handle* h, int head0, int nhead, int M, const float* x0, const f
   if (!fuse)
     RC(run_tdg(h, head0, nhead, td.guess, M, td.use_gpi, td.a, phi, td.gamma, td.next, td.next_stride, td.flag,
                td.xmax, td.poloff, td.dz_scale, td.prev, armed));
+  if (ex.skip_armed) *ex.skip_armed = armed;
+  const int tail_at = fuse ? 1 : 0;  // launch index of the loss tail (needs every row's loss)
+  const bool need_tail = losses || r || !fuse;  // losses, a w step or the Adam step bump
   BwdArgs A{};
-  A.xcd = nhead > 1 ? 1 : 0;
+  A.M = M;
+  A.head0 = head0;
   A.nhead = nhead;
+  A.xcd = nhead > 1 ? 1 : 0;
+  A.mask = h->mask;
+  A.hp = h->hp_psi;
+  A.hpw = h->hp_w;
+  A.x0 = x0;
+  A.phi = phi;
+  A.r = r;
+  A.train_w = r != nullptr;
+  A.losses = losses;
+  A.inc_step = ex.inc_step;
   A.step_in_tail = fuse ? 0 : 1;
   A.tdg_use_gpi = td.use_gpi;
   A.tdg_guess = td.guess;
@@ -718,44 +732,22 @@ int run_bwd(sfx_handle* h, int head0, int nhead, int M, const float* x0, const f
   A.flag = td.flag;
   A.flag_value = h->T;
   A.dz_scale = td.dz_scale;
-  if (armed && fuse) {
-    A.tdg_prev = td.prev;
-    A.skip = h->skip;
-    A.skipc = h->skipc;
-    A.skip_v0 = ex.skip_fwd ? 1 : 0;
-  }
+  A.xi_copy = td.xi_copy;
+  A.xi_n = td.xi_n;
+  A.dxs = 1;
   if (armed) {
     A.skip = h->skip;
     A.skip_v0 = ex.skip_fwd ? 1 : 0;
+    if (fuse) {  // the fused TD launch decides
+      A.tdg_prev = td.prev;
+      A.skipc = h->skipc;
+    }
   }
-  if (ex.skip_armed) *ex.skip_armed = armed;
-  const int tail_at = fuse ? 1 : 0;  // launch index of the loss tail (needs every row's loss)
-  const bool need_tail = losses || r || !fuse;  // losses, a w step or the Adam step bump
-  const double tdg_bytes = 4.0 * nhead * M * ((td.use_gpi ? h->T : 1) * h->O + 2.0 * h->O + 2.0 * h->d + 4);
-  A.M = M;
-  A.head0 = head0;
-  A.mask = h->mask;
-  A.hp = h->hp_psi;
-  A.hpw = h->hp_w;
-  A.x0 = x0;
-  A.phi = phi;
-  A.r = r;
-  A.train_w = r != nullptr;
-  A.losses = losses;
-  A.inc_step = ex.inc_step;
   auto dw_tiles = [&](int l) { return cdiv(h->L[l].N, 32) * cdiv(h->L[l].K, 64); };
   auto geo = [&](int l) {
     const LayerGeo& L = h->L[l];
-    RoleGeo r{};
-    r.N = L.N;
-    r.K = L.K;
-    r.wOff = L.wOff;
-    r.bOff = L.bOff;
-    r.actIn = L.actIn;
-    r.xOff = l == 0 ? -1 : h->actOff[l - 1];
-    r.dzOff = h->actOff[l];
-    r.dzIn = l == 0 ? 0 : h->actOff[l - 1];
-    return r;
+    const int xOff = l == 0 ? -1 : h->actOff[l - 1], dzIn = l == 0 ? 0 : h->actOff[l - 1];
+    return RoleGeo{L.N, L.K, L.wOff, L.bOff, L.actIn, xOff, /*dzOff*/ h->actOff[l], dzIn};
   };
   // algorithmic bytes: dX reads W, dZ, X and writes dZ_{l-1}; dW reads dZ, X and does Adam's
   // read p,m,v + write p,m,v (24 B per parameter)
@@ -767,6 +759,7 @@ int run_bwd(sfx_handle* h, int head0, int nhead, int M, const float* x0, const f
     const LayerGeo& L = h->L[l];
     return 24.0 * ((double)L.N * L.K + L.N) + 4.0 * ((double)M * L.N + (double)M * L.K);
   };
+  auto grid_of = [&](int ntile) { return A.xcd ? dim3(8 * cdiv(nhead, 8) * ntile) : dim3(ntile, nhead); };
   // Merged last launch: the only reader of the layer-1 dX launch's dZ_0 is the layer-0 dW tile of
   // the launch after it, and a tile needs just its own columns -- so each layer-0 tile (16 columns
   // wide here) computes them itself (role_dw<.., MG>) and the two launches become one: dW_2 || dW_1
@@ -775,57 +768,59 @@ int run_bwd(sfx_handle* h, int head0, int nhead, int M, const float* x0, const f
   // layer-0 tiles (one k-tile), no split-N dX, and a launch before it for the TD target.
   const bool merge = h->bwd_merge && nhead > 1 && !ex.ride && h->NL >= 3 && M <= 32 && ex.fuse_v0 &&
                      can_fuse_v0(h, M + (ex.v_xn ? 1 : 0)) && h->L[1].N <= DX_SPLIT_N;
-  for (int l = h->NL - 1; l >= (merge ? 2 : 1); --l) {
-    const int li = h->NL - 1 - l;
-    A.tdg = fuse && li == 0 ? 1 : 0;
-    A.xi_src = A.tdg ? td.xi_src : nullptr;
-    A.xi_dst = A.tdg ? td.xi_dst : nullptr;
-    A.xi_copy = td.xi_copy;
-    A.xi_n = td.xi_n;
-    const double by = nhead * (dx_bytes(l) + (l + 1 <= h->NL - 1 ? dw_bytes(l + 1) : 0.0)) + (A.tdg ? tdg_bytes : 0.0);
+  int l = h->NL - 1;  // the layer whose dX the next launch computes
+  if (fuse) {  // launch 0: the TD target with the last layer's dX
+    A.tdg = 1;
+    A.xi_src = td.xi_src;
+    A.xi_dst = td.xi_dst;
     A.ra = geo(l);
     A.na = cdiv(M, 32) * cdiv(h->L[l].K, 16);
-    // wide layers: the dX tiles split N in <= 256-wide chunks over workgroups (not in a fused
-    // TD launch)
-    A.dxs = 1;
-    if (!A.tdg && h->dxpart && h->L[l].N > DX_SPLIT_N && M <= 32 * cdiv(h->Mmax, 32) &&
-        nhead <= h->T) {
-      A.dxs = cdiv(h->L[l].N, DX_SPLIT_N);
+    const double tdg_bytes = 4.0 * nhead * M * ((td.use_gpi ? h->T : 1) * h->O + 2.0 * h->O + 2.0 * h->d + 4);
+    launch(h, K_BWD, nhead * dx_bytes(l) + tdg_bytes, tdg_variant(h) == 1 ? k_bwd_tdg<2, 8> : k_bwd_tdg<4, 4>,
+           grid_of(A.na), dim3(256), h->G, A);
+    A.tdg = 0;
+    A.xi_src = nullptr;
+    A.xi_dst = nullptr;
+    --l;
+  }
+  // A as launch li of the round: by the caller's ride-along hook (single-head callers), else the
+  // k_bwd (mg: k_bwd_mg) of the precision
+  auto issue = [&](int li, bool mg, double by) {
+    const int ntile = A.na + A.nb + A.nc + A.nd + A.tail;
+    if (ex.ride && nhead == 1 && ex.ride(li, tail_at, A, ntile, by)) return;
+    launch(h, K_BWD, by, !mg ? (h->bf16 ? k_bwd<true> : k_bwd<false>) : (h->bf16 ? k_bwd_mg<true> : k_bwd_mg<false>),
+           grid_of(ntile), dim3(256), h->G, A);
+  };
+  for (; l >= (merge ? 2 : 1); --l) {  // dX_l || dW_{l+1} (|| tail)
+    const int li = h->NL - 1 - l;
+    const bool dw = l < h->NL - 1;  // (not the unfused first launch)
+    A.ra = geo(l);
+    // wide layers: the dX tiles split N in <= 256-wide chunks over workgroups
+    const bool split = h->dxpart && h->L[l].N > DX_SPLIT_N && M <= 32 * cdiv(h->Mmax, 32) && nhead <= h->T;
+    A.dxs = split ? cdiv(h->L[l].N, DX_SPLIT_N) : 1;
+    A.na = cdiv(M, 32) * cdiv(h->L[l].K, 16) * A.dxs;
+    if (split) {
       A.dxpart = h->dxpart;
       A.dxctr = h->dxctr;
-      A.na *= A.dxs;
     }
-    if (l + 1 <= h->NL - 1) {
+    if (dw) {
       A.rb = geo(l + 1);
       A.nb = dw_tiles(l + 1);
-    } else {
-      A.nb = 0;
     }
-    A.nc = 0;
     A.tail = li == tail_at && need_tail ? 1 : 0;
-    const int ntile = A.tdg ? A.na : A.na + A.nb + A.nc + A.tail;
-    const dim3 grid = A.xcd ? dim3(8 * cdiv(nhead, 8) * ntile) : dim3(ntile, nhead);
-    if (A.tdg && tdg_variant(h) == 1)  // d <= 8
-      launch(h, K_BWD, by, k_bwd_tdg<2, 8>, grid, dim3(256), h->G, A);
-    else if (A.tdg)
-      launch(h, K_BWD, by, k_bwd_tdg<4, 4>, grid, dim3(256), h->G, A);
-    else if (!(ex.ride && nhead == 1 && !A.xcd && ex.ride(li, tail_at, A, ntile, by)))
-      launch(h, K_BWD, by, h->bf16 ? k_bwd<true> : k_bwd<false>, grid, dim3(256), h->G, A);
+    issue(li, false, nhead * (dx_bytes(l) + (dw ? dw_bytes(l + 1) : 0.0)));
   }
+  // last launch: dW_1 || dW_0 with the fused post-update forward (|| tail), or the merged one
+  const int last = merge ? h->NL - 2 : h->NL - 1;
   A.na = 0;
   A.dxs = 1;
-  A.tdg = 0;
-  A.xi_dst = nullptr;
-  A.xi_src = nullptr;
   A.rb = geo(1);
   A.nb = dw_tiles(1);
   A.rc = geo(0);
   A.nc = dw_tiles(0);
-  const int last = merge ? h->NL - 2 : h->NL - 1;  // index of this launch
   A.tail = last == tail_at && need_tail ? 1 : 0;
   double by_last = nhead * (dw_bytes(1) + dw_bytes(0));
   if (merge) {
-    A.merge = 1;
     A.nc = cdiv(h->L[0].N, 16);  // k_bwd_mg's layer-0 tiles are 16 columns wide (one k-tile: can_fuse_v0)
     A.ra = geo(1);
     A.rd = geo(2);
@@ -833,23 +828,19 @@ int run_bwd(sfx_handle* h, int head0, int nhead, int M, const float* x0, const f
     // + dX_1's W, dZ_1 and activation reads; dZ_0 is neither written nor read
     by_last += nhead * (dw_bytes(2) + dx_bytes(1) - 4.0 * M * h->L[1].K - 4.0 * M * h->L[0].N);
   }
-  A.fuse_v0 = ex.fuse_v0 ? 1 : 0;
   A.vM = M + (ex.v_xn ? 1 : 0);
   A.vOff = h->actOff[0];
   A.vRole = ex.vRole;
   A.act0 = h->L[0].actOut;
   A.v_x = ex.v_x;
   A.v_xn = ex.v_xn;
-  A.ax = ex.fuse_v0 ? ex.ax : nullptr;
-  A.aM = ex.fuse_v0 && ex.ax ? ex.aM : 0;
   A.a_noskip = ex.a_noskip;
-  const int ntile = A.nb + A.nc + A.nd + A.tail;
-  if (merge)  // nhead > 1: the XCD-aware 1-D grid
-    launch(h, K_BWD, by_last, h->bf16 ? k_bwd_mg<true> : k_bwd_mg<false>, dim3(8 * cdiv(nhead, 8) * ntile), dim3(256),
-           h->G, A);
-  else if (!(ex.ride && nhead == 1 && !A.xcd && ex.ride(h->NL - 1, tail_at, A, ntile, by_last)))
-    launch(h, K_BWD, by_last, h->bf16 ? k_bwd<true> : k_bwd<false>,
-           A.xcd ? dim3(8 * cdiv(nhead, 8) * ntile) : dim3(ntile, nhead), dim3(256), h->G, A);
+  if (ex.fuse_v0) {
+    A.fuse_v0 = 1;
+    A.ax = ex.ax;
+    A.aM = ex.ax ? ex.aM : 0;
+  }
+  issue(last, merge, by_last);
   LAUNCHCHK();
   return SFX_OK;
 }
@@ -1011,21 +1002,21 @@ void free_all(sfx_handle* h) {
 // (DESIGN.md §4), from 16 on the third device round.
 int auto_spec_rounds(int T_glob) { return T_glob >= 16 ? 3 : 2; }
 
-// Role of round r's post-update forward.  The launches of a round run in stream order, so every
-// round can write the same role (round r's TD launch has read round r-1's values before its
+// Role of every round's post-update forward.  The launches of a round run in stream order, so
+// every round can write the same role (round r's TD launch has read round r-1's values before its
 // forward overwrites them) -- which lets a head whose policy repeats round r-1 skip its forward.
-inline int round_role(const sfx_handle*, int) { return R_V; }
+constexpr int POST_ROLE = R_V;
 // next actions of speculative round r (two buffers: round r reads round r-1's while it writes)
 inline int64_t* spec_buf(sfx_handle* h, int r) { return h->spec_next + (size_t)(r & 1) * h->T * MMAX; }
 
 // One speculative round r of the all-task update: every policy takes its GPI next actions
 // with heads t < i seen through role `guess` (round 0: the pre-step heads), every head
 // updates from its read slot into its write slot, the post-update forward of S1 (++ s_next)
-// lands in round_role(r).  Only a final round runs k_ver (flag the first policy whose actions
+// lands in POST_ROLE.  Only a final round runs k_ver (flag the first policy whose actions
 // were wrong; action selection): an earlier round's verdict would be overwritten unread.
 int launch_round(sfx_handle* h, const sfx_handle::Pending& p, int r, bool final) {
   const int T = h->T, B = p.B;
-  const int guess = r == 0 ? R_S1 : round_role(h, r - 1), out = round_role(h, r);
+  const int guess = r == 0 ? R_S1 : POST_ROLE, out = POST_ROLE;
   const float* wsel = h->w + (size_t)p.task * h->dpad;
   TdgSpec td;
   td.use_gpi = p.use_gpi;
@@ -1040,7 +1031,7 @@ int launch_round(sfx_handle* h, const sfx_handle::Pending& p, int r, bool final)
   BwdExtra bx;
   bx.inc_step = r == 0 ? 1 : 0;  // later rounds redo the same optimizer step
   bool armed = false;
-  bx.skip_fwd = true;  // one role for every round (round_role)
+  bx.skip_fwd = true;  // one role for every round (POST_ROLE)
   bx.skip_armed = &armed;
   // the s_next row rides along in every round that a later round may skip heads after: a skipped
   // head's row must already be in the role when the final round's selection reads it

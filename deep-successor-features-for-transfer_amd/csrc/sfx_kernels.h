@@ -130,39 +130,28 @@ __device__ __forceinline__ bf16x8 ld_bf16x8(const __bf16* p) {  // 16-B aligned
   return *reinterpret_cast<const bf16x8*>(p);
 }
 
-// Loads / stores of data handed between workgroups INSIDE one launch (the split-N dX partial
-// tiles): C = true makes them coherent -- sc1 (L1-bypassing) dword loads and write-through
-// stores, the hand-off form of MI355X_MICROARCH.md's validated table (sc1 stores, every storing
-// wave's vmcnt(0), one agent-scope arrival per workgroup, sc1 poll, barrier, sc1 loads).
-// C = false: plain accesses (data from an earlier launch; the kernel boundary orders it).
-template <bool C>
-__device__ __forceinline__ float ldc(const float* p) {
-  if constexpr (C) return __hip_atomic_load(const_cast<float*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  else return *p;
+// Coherent dword load / store of data handed between workgroups INSIDE one launch (the split-N
+// dX partial tiles): sc1 (L1-bypassing) loads and write-through stores, the hand-off form of
+// MI355X_MICROARCH.md's validated table (sc1 stores, every storing wave's vmcnt(0), one
+// agent-scope arrival per workgroup, sc1 poll, barrier, sc1 loads).  Everything else is data from
+// an earlier launch -- the kernel boundary orders it -- and uses plain accesses.
+__device__ __forceinline__ float ld_coherent(const float* p) {
+  return __hip_atomic_load(const_cast<float*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-template <bool C>
-__device__ __forceinline__ void stc(float* p, float v) {
-#ifdef SFX_WT_ALL  // experiment: every hand-off store to a later launch write-through too
+__device__ __forceinline__ void st_coherent(float* p, float v) {
   __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#else
-  if constexpr (C) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  else *p = v;
-#endif
 }
-template <bool C>
-__device__ __forceinline__ float4 ldc4(const float* p) {  // 16-B aligned
-  if constexpr (C) return make_float4(ldc<true>(p), ldc<true>(p + 1), ldc<true>(p + 2), ldc<true>(p + 3));
-  else return *reinterpret_cast<const float4*>(p);
+__device__ __forceinline__ float4 ld4(const float* p) {  // 16-B aligned
+  return *reinterpret_cast<const float4*>(p);
 }
 
 // 16 consecutive floats row[kb .. kb+15] (zero where !ok / outside [0, K)).  `vec` must be
 // wave-uniform (K % 64 == 0 with 16-B aligned rows): then four predicated float4 loads.
-template <bool C = false>
 __device__ __forceinline__ void load16u(float (&v)[16], const float* row, int kb, int K, bool ok, bool vec) {
   if (vec) {
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      const float4 t = ok ? ldc4<C>(row + kb + 4 * q) : make_float4(0.f, 0.f, 0.f, 0.f);
+      const float4 t = ok ? ld4(row + kb + 4 * q) : make_float4(0.f, 0.f, 0.f, 0.f);
       v[4 * q] = t.x;
       v[4 * q + 1] = t.y;
       v[4 * q + 2] = t.z;
@@ -170,7 +159,7 @@ __device__ __forceinline__ void load16u(float (&v)[16], const float* row, int kb
     }
   } else {
 #pragma unroll
-    for (int j = 0; j < 16; ++j) v[j] = (ok && kb + j < K) ? ldc<C>(row + kb + j) : 0.f;
+    for (int j = 0; j < 16; ++j) v[j] = (ok && kb + j < K) ? *(row + kb + j) : 0.f;
   }
 }
 
@@ -335,24 +324,6 @@ struct AdamC {
   float omb1, b2, omb2, eps, wd, bc2s, nss;
 };
 
-template <bool C>
-__device__ __forceinline__ AdamC load_adamc(const AdamC* p) {
-  if constexpr (!C) {
-    return *p;
-  } else {
-    const float* f = reinterpret_cast<const float*>(p);
-    AdamC c;
-    c.omb1 = ldc<true>(f);
-    c.b2 = ldc<true>(f + 1);
-    c.omb2 = ldc<true>(f + 2);
-    c.eps = ldc<true>(f + 3);
-    c.wd = ldc<true>(f + 4);
-    c.bc2s = ldc<true>(f + 5);
-    c.nss = ldc<true>(f + 6);
-    return c;
-  }
-}
-
 __device__ __forceinline__ AdamC adam_consts(const AdamHP& hp, int step) {
   AdamC c;
   const double bc1 = 1.0 - pow(hp.b1, (double)step);
@@ -375,15 +346,8 @@ __device__ __forceinline__ AdamC adam_consts(const AdamHP& hp, int step) {
 __device__ __forceinline__ void st_wt(float* p, float v) {
   __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-#ifdef SFX_NO_WT  // diagnostics: the earlier stores (plain parameters, non-temporal moments)
-__device__ __forceinline__ void st_moment(float* p, float v) { __builtin_nontemporal_store(v, p); }
-template <bool C>
-__device__ __forceinline__ void st_param(float* p, float v) { stc<C>(p, v); }
-#else
 __device__ __forceinline__ void st_moment(float* p, float v) { st_wt(p, v); }
-template <bool C>
 __device__ __forceinline__ void st_param(float* p, float v) { st_wt(p, v); }
-#endif
 
 __device__ __forceinline__ void adam_apply(float& pp, float& mm, float& vv, float g, const AdamC& c) {
   if (c.wd != 0.f) g = __fadd_rn(g, __fmul_rn(c.wd, pp));
@@ -405,8 +369,8 @@ __device__ __forceinline__ void adam_el(float* p, float* m, float* v, float g, c
 // K1  Forward of one Linear (+activation) for a set of (role, head) instances:
 //   Y[M,N] = act(X[M,K] W[N,K]^T + b)      (nn.Linear of the ψ lambda,
 //                                            main_sfdqn_torch.py:57-71)
-// Grid: (ceil(N/16), n_inst, ceil(M/32)), 256 threads.  A workgroup owns a 32x16 output
-// tile; its 4 waves split K in 64-wide chunks, each wave runs two 16x16x4 f32 MFMA
+// Grid: (ceil(N/16), n_inst, ceil(M/32)), 64 * FWD_WAVES threads.  A workgroup owns a 32x16 output
+// tile; its waves split K in chunks of 256 / FWD_WAVES, each wave runs two 16x16x4 f32 MFMA
 // chains, partial tiles are summed through LDS in wave order (deterministic).
 // Instances come in up to 4 groups of consecutive heads sharing (role, param set, input).
 // Block (0,0,0) of a layer-0 launch may also run the env step's LMS reward fit
@@ -581,7 +545,8 @@ __device__ __forceinline__ FwdGroup fwd_group(const FwdArgs& F, int& y) {
   return g;
 }
 
-constexpr int FWD_TPW = 2;  // column tiles per workgroup (FwdArgs::tpw <= TP)
+constexpr int FWD_TPW = 2;    // column tiles per workgroup (FwdArgs::tpw <= TP)
+constexpr int FWD_WAVES = 8;  // waves per workgroup of k_fwd / k_fwd_tsf: they split K (fwd_tile)
 
 // row tiles of an m-row group (FwdArgs::tail: the last one covers up to 48 rows)
 __host__ __device__ __forceinline__ int fwd_row_tiles(int m, int tail) {
@@ -591,14 +556,13 @@ __host__ __device__ __forceinline__ int fwd_row_tiles(int m, int tail) {
 // TP > 1: the workgroup computes column tiles tN .. tN + tpw - 1 of its rows -- an L0 launch's
 // layer-0 rows computed once for them, a plain launch's X operands loaded once for them (launches
 // that would otherwise put more workgroups than CUs on the chip)
-template <bool VEC, int NW, bool L0, bool C, bool BF = false, int TP = 1>
+template <bool VEC, bool L0, bool BF = false, int TP = 1>
 __device__ __forceinline__ void fwd_tile(const Geo& G, const FwdArgs& F, int y, int tN, int tM, float* sT = nullptr) {
   constexpr int TPW = TP;
   static_assert(TP == 1 || VEC, "several tiles per workgroup: vector tiles only");
   const int ntile = TP == 1 ? 1 : (F.ntN - tN < F.tpw ? F.ntN - tN : F.tpw);
-  static_assert(!(L0 && C), "the in-tile layer 0 reads only inputs of earlier launches");
-  static_assert(!BF || (VEC && !C), "bf16 operands: vector tiles of plain launches");
-  constexpr int KW = 256 / NW;  // K chunk of one wave per iteration (NW waves cover 256)
+  static_assert(!BF || VEC, "bf16 operands: vector tiles only");
+  constexpr int KW = 256 / FWD_WAVES;  // K chunk of one wave per iteration (the waves cover 256)
   constexpr int KL = KW / 4;    // consecutive k per lane (4 lane groups per MFMA k-step)
   // instance -> (group, head) by scalar selects of each field (no dynamic kernarg indexing, and
   // no FwdGroup copy: conditionally copied structs were demoted to scratch, 17 dwords per lane)
@@ -615,7 +579,7 @@ __device__ __forceinline__ void fwd_tile(const Geo& G, const FwdArgs& F, int y, 
   const int ma = m0 + r, mb = m0 + 16 + r, mc = m0 + 32 + r;
   const bool oka = ma < M, okb = mb < M;
   // FwdArgs::tail: rows m0 + 32 .. m0 + 47 as a third MFMA block (block-uniform)
-  constexpr bool EXT = VEC && !L0 && !C;
+  constexpr bool EXT = VEC && !L0;
   const bool ext = EXT && F.tail && M - m0 > 32;
   const bool okc = ext && mc < M;
   const float* Pw = P + F.wOff;
@@ -631,7 +595,7 @@ __device__ __forceinline__ void fwd_tile(const Geo& G, const FwdArgs& F, int y, 
 #pragma unroll
   for (int j = 0; j < TPW; ++j) {
     const int col = (tN + j) * 16 + (Lx & 15);
-    biasv[j] = (j < ntile && threadIdx.x < (ext ? 192 : 128) && col < N) ? ldc<C>(P + F.bOff + col) : 0.f;
+    biasv[j] = (j < ntile && threadIdx.x < (ext ? 192 : 128) && col < N) ? *(P + F.bOff + col) : 0.f;
   }
   constexpr int AS = L0 ? L0_NMAX + 4 : 4;  // LDS row stride of a0 (padded against bank conflicts)
   __shared__ __align__(16) float sA[L0 ? 32 * AS : 4];
@@ -647,7 +611,7 @@ __device__ __forceinline__ void fwd_tile(const Geo& G, const FwdArgs& F, int y, 
       const bool ok = j < ntile && nj < N && kb0 < K;
 #pragma unroll
       for (int q = 0; q < KL / 4; ++q)
-        wpre[j][q] = ok ? ldc4<C>(Pw + (size_t)nj * K + kb0 + 4 * q) : make_float4(0.f, 0.f, 0.f, 0.f);
+        wpre[j][q] = ok ? ld4(Pw + (size_t)nj * K + kb0 + 4 * q) : make_float4(0.f, 0.f, 0.f, 0.f);
     }
   }
   if constexpr (BF && L0) {
@@ -663,7 +627,7 @@ __device__ __forceinline__ void fwd_tile(const Geo& G, const FwdArgs& F, int y, 
   if constexpr (L0) {
     __shared__ float sX[32 * L0_KMAX];
     const int K0 = F.K0;
-    // a0 = X W0ᵀ + b0 by MFMA: wave w owns layer-0 columns [32w, 32w + 32) (+32·NW ...), K0 in
+    // a0 = X W0ᵀ + b0 by MFMA: wave w owns layer-0 columns [32w, 32w + 32) (+32·FWD_WAVES ...), K0 in
     // k-steps of 4.  The W0 / b0 operands of the first column block are requested together
     // with the X rows, before the barrier (one memory latency, not one per k-step).
     const float* W0 = P + F.w0Off;
@@ -685,13 +649,13 @@ __device__ __forceinline__ void fwd_tile(const Geo& G, const FwdArgs& F, int y, 
     };
     int cb = wave * 32;
     load_w0(cb);
-    for (int j = threadIdx.x; j < 32 * K0; j += 64 * NW) {
+    for (int j = threadIdx.x; j < 32 * K0; j += 64 * FWD_WAVES) {
       const int rr = j / fdiv(K0), kk = j - rr * K0;
       sX[j] = m0 + rr < M ? X[(size_t)(m0 + rr) * K0 + kk] : 0.f;
     }
     __syncthreads();
     PROBE_AT(3);
-    for (; cb < K; cb += 32 * NW) {
+    for (; cb < K; cb += 32 * FWD_WAVES) {
       floatx4 c00 = {0.f, 0.f, 0.f, 0.f}, c01 = c00, c10 = c00, c11 = c00;
 #pragma unroll
       for (int q = 0; q < KS; ++q) {
@@ -726,7 +690,7 @@ __device__ __forceinline__ void fwd_tile(const Geo& G, const FwdArgs& F, int y, 
       put(c01, 1);
       put(c10, 2);
       put(c11, 3);
-      if (cb + 32 * NW < K) load_w0(cb + 32 * NW);
+      if (cb + 32 * FWD_WAVES < K) load_w0(cb + 32 * FWD_WAVES);
     }
     __syncthreads();
     PROBE_AT(4);
@@ -734,7 +698,7 @@ __device__ __forceinline__ void fwd_tile(const Geo& G, const FwdArgs& F, int y, 
   const float* xra = L0 ? sA + r * AS : X + (size_t)ma * K;
   const float* xrb = L0 ? sA + (16 + r) * AS : X + (size_t)mb * K;
   const float* xrc = X + (size_t)(okc ? mc : 0) * K;
-  __shared__ floatx4 red[NW][EXT ? 3 : 2][64];
+  __shared__ floatx4 red[FWD_WAVES][EXT ? 3 : 2][64];
   floatx4 acc0[TPW], acc1[TPW], acc2[EXT ? TPW : 1];
 #pragma unroll
   for (int j = 0; j < TPW; ++j) acc0[j] = acc1[j] = floatx4{0.f, 0.f, 0.f, 0.f};
@@ -811,24 +775,24 @@ __device__ __forceinline__ void fwd_tile(const Geo& G, const FwdArgs& F, int y, 
           ta = reinterpret_cast<const float4*>(xra + kb)[q];
           tb = reinterpret_cast<const float4*>(xrb + kb)[q];
         } else {
-          ta = oka ? ldc4<C>(xra + kb + 4 * q) : make_float4(0.f, 0.f, 0.f, 0.f);
-          tb = okb ? ldc4<C>(xrb + kb + 4 * q) : make_float4(0.f, 0.f, 0.f, 0.f);
+          ta = oka ? ld4(xra + kb + 4 * q) : make_float4(0.f, 0.f, 0.f, 0.f);
+          tb = okb ? ld4(xrb + kb + 4 * q) : make_float4(0.f, 0.f, 0.f, 0.f);
         }
 #pragma unroll
         for (int j = 0; j < TPW; ++j) {
           float4 tw;
           if constexpr (L0 && !BF) {
             tw = kc == wave * KW ? wpre[j][q]
-                                 : (oknj[j] ? ldc4<C>(wrj[j] + kb + 4 * q) : make_float4(0.f, 0.f, 0.f, 0.f));
+                                 : (oknj[j] ? ld4(wrj[j] + kb + 4 * q) : make_float4(0.f, 0.f, 0.f, 0.f));
           } else {
-            tw = oknj[j] ? ldc4<C>(wrj[j] + kb + 4 * q) : make_float4(0.f, 0.f, 0.f, 0.f);
+            tw = oknj[j] ? ld4(wrj[j] + kb + 4 * q) : make_float4(0.f, 0.f, 0.f, 0.f);
           }
           bw[j][4 * q] = tw.x; bw[j][4 * q + 1] = tw.y; bw[j][4 * q + 2] = tw.z; bw[j][4 * q + 3] = tw.w;
         }
         a0[4 * q] = ta.x; a0[4 * q + 1] = ta.y; a0[4 * q + 2] = ta.z; a0[4 * q + 3] = ta.w;
         a1[4 * q] = tb.x; a1[4 * q + 1] = tb.y; a1[4 * q + 2] = tb.z; a1[4 * q + 3] = tb.w;
         if constexpr (EXT) {
-          const float4 tc = okc ? ldc4<C>(xrc + kb + 4 * q) : make_float4(0.f, 0.f, 0.f, 0.f);
+          const float4 tc = okc ? ld4(xrc + kb + 4 * q) : make_float4(0.f, 0.f, 0.f, 0.f);
           a2[4 * q] = tc.x; a2[4 * q + 1] = tc.y; a2[4 * q + 2] = tc.z; a2[4 * q + 3] = tc.w;
         }
       }
@@ -840,11 +804,11 @@ __device__ __forceinline__ void fwd_tile(const Geo& G, const FwdArgs& F, int y, 
           a0[i] = (oka && kin) ? xra[kb + i] : 0.f;
           a1[i] = (okb && kin) ? xrb[kb + i] : 0.f;
         } else {
-          a0[i] = (oka && kin) ? ldc<C>(xra + kb + i) : 0.f;
-          a1[i] = (okb && kin) ? ldc<C>(xrb + kb + i) : 0.f;
+          a0[i] = (oka && kin) ? *(xra + kb + i) : 0.f;
+          a1[i] = (okb && kin) ? *(xrb + kb + i) : 0.f;
         }
 #pragma unroll
-        for (int j = 0; j < TPW; ++j) bw[j][i] = (oknj[j] && kin) ? ldc<C>(wrj[j] + kb + i) : 0.f;
+        for (int j = 0; j < TPW; ++j) bw[j][i] = (oknj[j] && kin) ? *(wrj[j] + kb + i) : 0.f;
       }
     }
 #pragma unroll
@@ -877,7 +841,7 @@ __device__ __forceinline__ void fwd_tile(const Geo& G, const FwdArgs& F, int y, 
     const int s = threadIdx.x >> 6;
     floatx4 v = red[0][s][Lx];
 #pragma unroll
-    for (int w2 = 1; w2 < NW; ++w2) v += red[w2][s][Lx];
+    for (int w2 = 1; w2 < FWD_WAVES; ++w2) v += red[w2][s][Lx];
     if (col < N) {
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
@@ -885,7 +849,7 @@ __device__ __forceinline__ void fwd_tile(const Geo& G, const FwdArgs& F, int y, 
         const float o = act_fwd(__fadd_rn(v[i], bias), F.act);
         if (row < M) {
           G.chk_act(F.yOff, (long long)row * N + col);
-          stc<C>(Y + (size_t)row * N + col, o);
+          Y[(size_t)row * N + col] = o;
         }
         if (sT) sT[(row - m0) * 16 + (col - n0)] = row < M ? o : 0.f;
       }
@@ -897,7 +861,7 @@ __device__ __forceinline__ void fwd_tile(const Geo& G, const FwdArgs& F, int y, 
 constexpr int qa_tile_floats(bool L0) { return L0 ? 1 : 32 * 16; }  // L0 launches never accumulate
 
 // workgroup (bx, by, bz) of a forward launch's grid (k_fwd; k_fwd_tsf after its TSF blocks)
-template <bool VEC, int NW, bool L0, bool BF, int TP>
+template <bool VEC, bool L0, bool BF, int TP>
 __device__ __forceinline__ void fwd_body(const Geo& G, const FwdArgs& F, int bx, int by, int bz) {
   PROBE_T(pt0);
   int y = by, tN = bx, tM = bz;
@@ -948,7 +912,7 @@ __device__ __forceinline__ void fwd_body(const Geo& G, const FwdArgs& F, int bx,
     }
   }
   __shared__ float sT[qa_tile_floats(L0)];
-  fwd_tile<VEC, NW, L0, false, BF, TP>(G, F, y, tN, tM, qa ? sT : nullptr);
+  fwd_tile<VEC, L0, BF, TP>(G, F, y, tN, tM, qa ? sT : nullptr);
   if (qa) q_accumulate(G, F, head, tN, tM, sT);
   if (tN == 0 && tM == 0 && by == 0 && (F.xcd ? bx == 0 : true)) {
     if (F.flag && threadIdx.x == 0) *F.flag = F.flag_value;
@@ -957,9 +921,9 @@ __device__ __forceinline__ void fwd_body(const Geo& G, const FwdArgs& F, int bx,
   PROBE_REC(L0 ? 2 : 1, pt0);
 }
 
-template <bool VEC, int NW, bool L0, bool BF = false, int TP = 1>
-__global__ __launch_bounds__(64 * NW) void k_fwd(Geo G, FwdArgs F) {
-  fwd_body<VEC, NW, L0, BF, TP>(G, F, blockIdx.x, blockIdx.y, blockIdx.z);
+template <bool VEC, bool L0, bool BF = false, int TP = 1>
+__global__ __launch_bounds__(64 * FWD_WAVES) void k_fwd(Geo G, FwdArgs F) {
+  fwd_body<VEC, L0, BF, TP>(G, F, blockIdx.x, blockIdx.y, blockIdx.z);
 }
 
 // K1b  Forward of a wide layer (N >= GEMV_N) for a few rows (M <= GEMV_M: the B = 1 action
@@ -1199,14 +1163,16 @@ __global__ __launch_bounds__(256) void k_tdg(Geo G, TdgArgs A) {
 //   dW role : dW_l = dZ_l^T X_l ; db_l = Σ_m dZ_l ; Adam(W_l, b_l) read slot -> write slot
 //   tail    : (first launch only) l1 from the per-row losses, optional l2 = MSE(w_i·φ, r)
 //             with one Adam step on w_i (sfdqn.py:340-342), Adam step counter += 1.
-// Layers are walked in a ping-pong (dX of l with dW of l+1) so each launch needs only one
-// dZ.  With fuse_v0 the layer-0 dW tiles also run the post-update forward of layer 0 for
-// the rows of S1 (and s_next) into R_V from the freshly written parameters.
-// The merged last launch (BwdArgs::merge) folds the layer-1 dX into the layer-0 dW tiles: each
-// computes the 32 columns of dZ_0 it consumes (two dX tiles of layer 1) into LDS, so dZ_0 never
-// goes through memory and dW_2 (role rd) runs beside dW_1 and the layer-0 tiles.
-// blockIdx.x selects the role, longest first: [0, nc) dW rc; then nd dW rd; nb dW rb; na dX; tail.
-// blockIdx.y = head - head0.
+// Launches of a round for the NL-Linear net (run_bwd), a ping-pong so that each needs
+// only one dZ: TD target + dX of the last layer (k_bwd_tdg); dX_l ∥ dW_{l+1} (∥ tail) for
+// l = NL-2 .. 1 (k_bwd); dW_1 ∥ dW_0 (k_bwd).  With fuse_v0 the layer-0 dW tiles also run the
+// post-update forward of layer 0 for the rows of S1 (and s_next) into R_V from the freshly written
+// parameters.
+// The many-head callers end with the merged launch instead (k_bwd_mg): dW_2 (role rd) ∥ dW_1 ∥
+// layer-0 tiles 16 columns wide, each computing the 16 columns of dZ_0 it consumes -- one dX tile
+// of layer 1 (role ra) -- into LDS, so dZ_0 never goes through memory and the dX_1 launch is gone.
+// blockIdx.x selects the role, longest first: [0, nc) dW rc (layer 0); then nd dW rd; nb dW rb;
+// na dX; tail.  blockIdx.y = head - head0 (or both from an XCD-aware 1-D grid: BwdArgs::xcd).
 // -------------------------------------------------------------------------------------
 struct RoleGeo {
   int N, K, wOff, bOff, actIn;
@@ -1266,10 +1232,10 @@ struct BwdArgs {
   int* skip;
   unsigned long long* skipc;
   int skip_v0;         // skipped heads' layer-0 tiles: 1 = the post-update forward skips them too
-  int merge;           // 1: k_bwd_mg -- the rc (layer-0) tiles compute their own dZ_0 = dX of layer ra from dZ_1
   // learned φ (features/deep_phi.py): the output gradient scaled by λ (device scalar)
   const float* dz_scale;
 };
+static_assert(sizeof(BwdArgs) == 512, "BwdArgs: the kernel-argument layout of k_bwd* / k_bwd_tsf");
 
 __device__ __forceinline__ const float* layer_input(const Geo& G, const BwdArgs& A, int head, int xOff) {
   return xOff < 0 ? A.x0 : G.actp(R_S, head, xOff);
@@ -1292,7 +1258,7 @@ struct TdgSmem {
 
 // Returns 1 when the policy repeats the previous round's update (BwdArgs::tdg_prev): then the
 // output gradient and the row losses are left as that round wrote them.
-template <int VMAX, int U, bool C>
+template <int VMAX, int U>
 __device__ int tdg_rows(const Geo& G, const BwdArgs& A, int pol, int m0, bool pub, TdgSmem& sm) {
   const int tid = threadIdx.x, T = G.T, Aa = G.A, d = G.d, O = G.O, NLm = G.lastOff, M = A.M;
   const int nb = M - m0 < 32 ? M - m0 : 32;
@@ -1438,15 +1404,7 @@ __device__ int tdg_rows(const Geo& G, const BwdArgs& A, int pol, int m0, bool pu
     float4* gout4 = reinterpret_cast<float4*>(G.dzp(pol, NLm) + (size_t)m0 * O);
     for (int i = tid; i < n4; i += 256) {
       const float4 v = reinterpret_cast<const float4*>(sm.dz)[i];
-      if constexpr (C) {
-        float* o = reinterpret_cast<float*>(gout4 + i);
-        stc<true>(o, v.x);
-        stc<true>(o + 1, v.y);
-        stc<true>(o + 2, v.z);
-        stc<true>(o + 3, v.w);
-      } else {
-        gout4[i] = v;
-      }
+      gout4[i] = v;
     }
     for (int bl = tid; bl < nb; bl += 256) {  // row Σ diff^2 in feature order
       float sacc = 0.f;
@@ -1474,13 +1432,13 @@ struct DxOps {
 };
 
 // chunk nc (columns nc + 16 g ..) of the wave; nc >= nend: all zeros
-template <bool C, bool BF, int NS>
+template <bool BF, int NS>
 __device__ __forceinline__ void dx_load(DxOps<BF, NS>& o, const float* dZ, const float* W, const __bf16* W16, int N, int K,
                                         int nc, int nend, int ma, int mb, bool oka, bool okb, const int (&kk)[NS]) {
   const int nb = nc + ((threadIdx.x & 63) >> 4) * 16;
   const bool vec = (N & 63) == 0, in = nc < nend;
-  load16u<C>(o.a0, dZ + (size_t)ma * N, nb, nend, oka && in, vec);
-  load16u<C>(o.a1, dZ + (size_t)mb * N, nb, nend, okb && in, vec);
+  load16u(o.a0, dZ + (size_t)ma * N, nb, nend, oka && in, vec);
+  load16u(o.a1, dZ + (size_t)mb * N, nb, nend, okb && in, vec);
 #pragma unroll
   for (int s = 0; s < NS; ++s) {
 #pragma unroll
@@ -1516,13 +1474,13 @@ __device__ __forceinline__ void dx_mma(const DxOps<BF, NS>& o, floatx4 (&acc)[NS
   }
 }
 
-template <bool C, bool BF, int NS>
+template <bool BF, int NS>
 __device__ __forceinline__ void dx_accum(const float* dZ, const float* W, const __bf16* W16, int N, int K, int nbeg,
                                          int nend, int ma, int mb, bool oka, bool okb, const int (&kk)[NS],
                                          floatx4 (&acc)[NS][2]) {
   for (int nc = nbeg + (threadIdx.x >> 6) * 64; nc < nend; nc += 256) {
     DxOps<BF, NS> o;
-    dx_load<C, BF, NS>(o, dZ, W, W16, N, K, nc, nend, ma, mb, oka, okb, kk);
+    dx_load<BF, NS>(o, dZ, W, W16, N, K, nc, nend, ma, mb, oka, okb, kk);
     dx_mma<BF, NS>(o, acc);
   }
 }
@@ -1537,9 +1495,9 @@ __device__ __forceinline__ floatx4 dx_red_sum(const floatx4 (*red)[2][64], int s
   return v;
 }
 
-template <bool TDG, int VMAX = 2, int U = 8, bool C = false, bool BF = false>
+template <bool TDG, int VMAX = 2, int U = 8, bool BF = false>
 __device__ __forceinline__ void role_dx(const Geo& G, const BwdArgs& A, int head, int tile, floatx4 (*red)[2][64]) {
-  static_assert(!(BF && (TDG || C)), "bf16 dX: the plain dX tiles only (the fused TD launch stays fp32)");
+  static_assert(!(BF && TDG), "bf16 dX: the plain dX tiles only (the fused TD launch stays fp32)");
   const RoleGeo L = A.ra;
   const int N = L.N, K = L.K, M = A.M;
   const int ntk = (K + 15) >> 4;
@@ -1572,20 +1530,8 @@ __device__ __forceinline__ void role_dx(const Geo& G, const BwdArgs& A, int head
     if (tile == 0 && A.inc_step && threadIdx.x == 0 && !step_cancelled(G.cancel)) {  // no dW reads them in this launch
       const int st = G.step[head] + 1;
       const AdamC ac = adam_consts(A.hp, st);
-      if constexpr (C) {  // read by this launch's dW tiles
-        __hip_atomic_store(G.step + head, st, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        float* f = reinterpret_cast<float*>(G.adamc + head);
-        stc<true>(f, ac.omb1);
-        stc<true>(f + 1, ac.b2);
-        stc<true>(f + 2, ac.omb2);
-        stc<true>(f + 3, ac.eps);
-        stc<true>(f + 4, ac.wd);
-        stc<true>(f + 5, ac.bc2s);
-        stc<true>(f + 6, ac.nss);
-      } else {
-        G.step[head] = st;
-        G.adamc[head] = ac;
-      }
+      G.step[head] = st;
+      G.adamc[head] = ac;
     }
     if (A.flag && tile == 0 && head == A.head0 && threadIdx.x == 0) *A.flag = A.flag_value;
     // the 16 k-steps of each 64-wide chunk are split over the waves (4 or 8 steps each); the
@@ -1596,7 +1542,7 @@ __device__ __forceinline__ void role_dx(const Geo& G, const BwdArgs& A, int head
 #pragma unroll
     for (int j = 0; j < 16; ++j)
       bw[j] = (j >= j0 && j < j0 + jw && okk && nb + j < N) ? W[(size_t)(nb + j) * K + kk] : 0.f;
-    if (tdg_rows<VMAX, U, C>(G, A, head, m0, tile % ntk == 0, sm)) return;  // repeats round r-1 (block-uniform)
+    if (tdg_rows<VMAX, U>(G, A, head, m0, tile % ntk == 0, sm)) return;  // repeats round r-1 (block-uniform)
     const float* da = sm.dz + (size_t)r * N + nb;
     const float* db = sm.dz + (size_t)(16 + r) * N + nb;
 #pragma unroll
@@ -1610,8 +1556,8 @@ __device__ __forceinline__ void role_dx(const Geo& G, const BwdArgs& A, int head
   } else {
     const int kks[1] = {kk};
     floatx4 acc[1][2] = {{acc0, acc1}};
-    dx_accum<C, BF, 1>(G.dzp(head, L.dzOff), W, BF ? G.on16 + G.slot_off(rslot(A.mask, head), head) + L.wOff : nullptr, N, K,
-                       nbeg, nend, ma, mb, oka, okb, kks, acc);
+    dx_accum<BF, 1>(G.dzp(head, L.dzOff), W, BF ? G.on16 + G.slot_off(rslot(A.mask, head), head) + L.wOff : nullptr, N, K,
+                    nbeg, nend, ma, mb, oka, okb, kks, acc);
     acc0 = acc[0][0];
     acc1 = acc[0][1];
   }
@@ -1630,7 +1576,7 @@ __device__ __forceinline__ void role_dx(const Geo& G, const BwdArgs& A, int head
       SFX_CHK((long long)((pt + split) * 128 + threadIdx.x) * 4 + 3 < G.ext_dxpart, pt, split, G.ext_dxpart);
 #endif
 #pragma unroll
-      for (int i = 0; i < 4; ++i) stc<true>(o + i, v[i]);
+      for (int i = 0; i < 4; ++i) st_coherent(o + i, v[i]);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
     __syncthreads();
@@ -1646,7 +1592,7 @@ __device__ __forceinline__ void role_dx(const Geo& G, const BwdArgs& A, int head
     for (int q = 0; q < A.dxs; ++q) {
       const float* o = A.dxpart + ((pt + q) * 128 + threadIdx.x) * 4;
 #pragma unroll
-      for (int i = 0; i < 4; ++i) v[i] = __fadd_rn(v[i], ldc<true>(o + i));
+      for (int i = 0; i < 4; ++i) v[i] = __fadd_rn(v[i], ld_coherent(o + i));
     }
     if (col < K) {
 #pragma unroll
@@ -1654,7 +1600,7 @@ __device__ __forceinline__ void role_dx(const Geo& G, const BwdArgs& A, int head
         const int row = m0 + 16 * s + (Lx >> 4) * 4 + i;
         if (row < M) {
           G.chk_act(L.dzIn, (long long)row * K + col);
-          stc<C>(out + (size_t)row * K + col, act_bwd(v[i], xin[i], L.actIn));
+          out[(size_t)row * K + col] = act_bwd(v[i], xin[i], L.actIn);
         }
       }
     }
@@ -1668,7 +1614,7 @@ __device__ __forceinline__ void role_dx(const Geo& G, const BwdArgs& A, int head
         const int row = m0 + 16 * s + (Lx >> 4) * 4 + i;
         if (row < M) {
           G.chk_act(L.dzIn, (long long)row * K + col);
-          stc<C>(out + (size_t)row * K + col, act_bwd(v[i], xin[i], L.actIn));
+          out[(size_t)row * K + col] = act_bwd(v[i], xin[i], L.actIn);
         }
       }
     }
@@ -1688,7 +1634,6 @@ constexpr int V0S = KFUSE + 4;  // LDS row stride of the tile's weights: lane (r
 // stride K, `rows` valid) times this lane's weight row w (K floats), bias bb, into Y (row stride
 // N).  Every LDS operand is read before the first MFMA (K <= KFUSE: at most 16 k-steps), in the
 // k-ordered accumulation of k_fwd's layer-0 path.
-template <bool C>
 __device__ __forceinline__ void v0_tile(const float* x, int K, int m0, int rows, const float* w, float bb, int act,
                                         float* Y, int N, int n, long long lim) {
   constexpr int KS = 8;  // k-steps whose operands are read together (K <= 32: one batch)
@@ -1712,13 +1657,13 @@ __device__ __forceinline__ void v0_tile(const float* x, int K, int m0, int rows,
       const int m = m0 + g * 4 + i;
       if (m < rows) {
         SFX_CHK((long long)m * N + n < lim, m, n, lim);
-        stc<C>(Y + (size_t)m * N + n, act_fwd(__fadd_rn(c[i], bb), act));
+        Y[(size_t)m * N + n] = act_fwd(__fadd_rn(c[i], bb), act);
       }
     }
   }
 }
 
-template <bool C, int NW = 32>
+template <int NW = 32>
 __device__ __forceinline__ void fused_v0(const Geo& G, const BwdArgs& A, const RoleGeo& L, int head, int nbase, const float* sW,
                          const float* sB, const float* sX, const float* sWt = nullptr, const float* sBt = nullptr,
                          bool vrows = true, bool landed = false) {
@@ -1738,7 +1683,7 @@ __device__ __forceinline__ void fused_v0(const Geo& G, const BwdArgs& A, const R
   if (vrows) {
     float* Y = G.actp(A.vRole, head, A.vOff);
     for (int mt = wt; mt * 16 < VM; mt += WS)
-      v0_tile<C>(sX, K, mt * 16, VM, sW + nl * V0S, bias, A.act0, Y, N, n, G.actSize - A.vOff);
+      v0_tile(sX, K, mt * 16, VM, sW + nl * V0S, bias, A.act0, Y, N, n, G.actSize - A.vOff);
   }
   PROBE_AT(4);
   if (A.aM > 0) {
@@ -1749,9 +1694,9 @@ __device__ __forceinline__ void fused_v0(const Geo& G, const BwdArgs& A, const R
     const float bt = sBt[nl];
     for (int it = wt; it < 3 * nt; it += WS) {
       const int which = it / nt, mt = it - which * nt;
-      v0_tile<C>(xa + (which ? aM * K : 0), K, mt * 16, aM, which == 2 ? sWt + nl * K : sW + nl * V0S,
-                 which == 2 ? bt : bias, A.act0, G.actp(which == 0 ? R_NS : which == 1 ? R_NS1 : R_NS1T, head, A.vOff),
-                 N, n, G.actSize - A.vOff);
+      v0_tile(xa + (which ? aM * K : 0), K, mt * 16, aM, which == 2 ? sWt + nl * K : sW + nl * V0S,
+              which == 2 ? bt : bias, A.act0, G.actp(which == 0 ? R_NS : which == 1 ? R_NS1 : R_NS1T, head, A.vOff),
+              N, n, G.actSize - A.vOff);
     }
   }
   PROBE_AT(5);
@@ -1836,7 +1781,7 @@ __device__ __forceinline__ void role_v0_only(const Geo& G, const BwdArgs& A, int
     const int nxs = A.vM * K;
     for (int j = tid; j < nxs; j += 256) sX[j] = j < M * K ? A.v_x[j] : A.v_xn[j - M * K];
   }
-  fused_v0<false, NW>(G, A, L, head, nbase, sW, sB, sX, sm.sWt, sm.sBt, vrows);
+  fused_v0<NW>(G, A, L, head, nbase, sW, sB, sX, sm.sWt, sm.sBt, vrows);
 }
 
 // MG (layer-0 tiles of the merged launch; M <= 32, one k-tile, no split N): a tile is 16 columns
@@ -1846,7 +1791,7 @@ __device__ __forceinline__ void role_v0_only(const Geo& G, const BwdArgs& A, int
 // whose per-wave partial sums meet in red; every lane then sums the four waves' partials of the
 // eight dZ elements its dW MFMAs take.  Wave w takes the one 16-wide k group 16 w.. of the dW
 // block (each dW element is one MFMA chain over the rows, whichever wave runs it).
-template <bool C = false, bool BF = false, bool MG = false>
+template <bool BF = false, bool MG = false>
 __device__ __forceinline__ void role_dw(const Geo& G, const BwdArgs& A, int head, const RoleGeo& L, int tile, bool fuse,
                                         floatx4 (*red)[2][64] = nullptr) {
   constexpr int NW = MG ? 16 : 32;  // tile width
@@ -1867,7 +1812,7 @@ __device__ __forceinline__ void role_dw(const Geo& G, const BwdArgs& A, int head
   float* Pw = G.online + wo;
   float* Mw = G.am + wo;
   float* Vw = G.av + wo;
-  const AdamC c = load_adamc<C>(G.adamc + head);  // bias corrections of this step (double pow once per head)
+  const AdamC c = G.adamc[head];  // bias corrections of this step (double pow once per head)
   const int cx = step_cancelled(G.cancel);
   const int nn = n0 + r, kb0 = k0 + r, kb1 = k0 + 16 + r;
   // prefetch the optimizer state of the 8 (MG: 4) weights this lane will update
@@ -1948,8 +1893,8 @@ __device__ __forceinline__ void role_dw(const Geo& G, const BwdArgs& A, int head
     }
     const int kks[1] = {nbase + r};
     floatx4 dacc[1][2] = {};
-    dx_accum<false, BF, 1>(G.dzp(head, L1.dzOff), Pr + L1.wOff, BF ? G.on16 + ro + L1.wOff : nullptr, L1.N, L1.K, 0, L1.N, r,
-                           16 + r, r < M, 16 + r < M, kks, dacc);
+    dx_accum<BF, 1>(G.dzp(head, L1.dzOff), Pr + L1.wOff, BF ? G.on16 + ro + L1.wOff : nullptr, L1.N, L1.K, 0, L1.N, r,
+                    16 + r, r < M, 16 + r < M, kks, dacc);
     red[wave][0][lane] = dacc[0][0];
     red[wave][1][lane] = dacc[0][1];
     PROBE_AT(6);
@@ -1977,7 +1922,7 @@ __device__ __forceinline__ void role_dw(const Geo& G, const BwdArgs& A, int head
         bv0[j] = xb0[j];
         continue;
       }
-      av[j] = (okm && nn < N) ? ldc<C>(dZ + (size_t)m * N + nn) : 0.f;
+      av[j] = (okm && nn < N) ? dZ[(size_t)m * N + nn] : 0.f;
       bv0[j] = (okm && kb0 < K) ? X[(size_t)m * K + kb0] : 0.f;
       bv1[j] = (okm && kb1 < K) ? X[(size_t)m * K + kb1] : 0.f;
     }
@@ -2026,7 +1971,7 @@ __device__ __forceinline__ void role_dw(const Geo& G, const BwdArgs& A, int head
         SFX_CHK((long long)off < G.P, L.wOff, n, k);
         adam_apply(pp[e], pm[e], pv[e], h ? acc1[i] : acc0[i], c);
         if (!cx) {
-          st_param<C>(Pw + off, pp[e]);
+          st_param(Pw + off, pp[e]);
           st_moment(Mw + off, pm[e]);
           st_moment(Vw + off, pv[e]);
           // the bf16 copy of the write slot (2-byte stores: an LDS transpose into 16-byte row stores
@@ -2040,14 +1985,14 @@ __device__ __forceinline__ void role_dw(const Geo& G, const BwdArgs& A, int head
   if (dob) {
     adam_apply(bp, bm, bv, bsum, c);
     if (!cx) {
-      st_param<C>(Pw + L.bOff + nbias, bp);
+      st_param(Pw + L.bOff + nbias, bp);
       st_moment(Mw + L.bOff + nbias, bm);
       st_moment(Vw + L.bOff + nbias, bv);
       if constexpr (BF) G.on16[wo + L.bOff + nbias] = (__bf16)bp;
     }
     if (fuse) sB[nbias - nbase] = bp;
   }
-  if (fuse) fused_v0<C, NW>(G, A, L, head, nbase, sW, sB, sX, sm.sWt, sm.sBt, true, true);
+  if (fuse) fused_v0<NW>(G, A, L, head, nbase, sW, sB, sX, sm.sWt, sm.sBt, true, true);
 }
 
 // loss finalisation, optional w step, Adam step counter (one workgroup per head)
@@ -2135,28 +2080,28 @@ __device__ __forceinline__ void bwd_body(const Geo& G, const BwdArgs& A, int hea
       if (A.fuse_v0 && (!A.skip_v0 || (A.aM > 0 && A.a_noskip))) role_v0_only<MG ? 16 : 32>(G, A, head, A.rc, bx, !A.skip_v0);
       return;
     }
-    role_dw<false, BF, MG>(G, A, head, A.rc, bx, A.fuse_v0 != 0, red);
+    role_dw<BF, MG>(G, A, head, A.rc, bx, A.fuse_v0 != 0, red);
     PROBE_REC(6, pt0);
     return;
   }
   bx -= A.nc;
   if (bx < A.nd) {
     if (skip) return;
-    role_dw<false, BF>(G, A, head, A.rd, bx, false);
+    role_dw<BF>(G, A, head, A.rd, bx, false);
     PROBE_REC(5, pt0);
     return;
   }
   bx -= A.nd;
   if (bx < A.nb) {
     if (skip) return;
-    role_dw<false, BF>(G, A, head, A.rb, bx, false);
+    role_dw<BF>(G, A, head, A.rb, bx, false);
     PROBE_REC(5, pt0);
     return;
   }
   bx -= A.nb;
   if (bx < A.na) {
     if (skip) return;
-    role_dx<false, 2, 8, false, BF>(G, A, head, bx, red);
+    role_dx<false, 2, 8, BF>(G, A, head, bx, red);
     PROBE_REC(4, pt0);
     return;
   }

@@ -59,17 +59,6 @@ __device__ __forceinline__ float4 phiw_ld4(const float* row, int k, int K, bool 
   return v;
 }
 
-__device__ __forceinline__ float2 phiw_ld2(const float* row, int k, int K, bool vec) {
-  float2 v = make_float2(0.f, 0.f);
-  if (vec) {
-    if (k < K) v = *reinterpret_cast<const float2*>(row + k);
-  } else {
-    if (k < K) v.x = row[k];
-    if (k + 1 < K) v.y = row[k + 1];
-  }
-  return v;
-}
-
 // the layer-0 input s ⊕ a ⊕ s1, kept for dW
 __global__ __launch_bounds__(256) void k_phiw_in(float* x, const float* S, const int64_t* a, const float* S1, int B,
                                                  int n_s) {

@@ -126,7 +126,7 @@ int shard_begin_body(sfx_handle* h, const sfx_handle::Pending& p, int lms_task, 
 // S1 ++ s_next (fused: which accumulates the next round's maxima, all-reduced right after;
 // final rounds also fill the selection table)
 int shard_round_body(sfx_handle* h, const sfx_handle::Pending& p, int r, bool final) {
-  const int guess = r == 0 ? R_S1 : round_role(h, r - 1), out = round_role(h, r);
+  const int guess = r == 0 ? R_S1 : POST_ROLE, out = POST_ROLE;
   const bool fused = shard_fused(h, p.B);
   const size_t body = shard_body(h, p.B), tail = (size_t)h->Tg * h->A;
   int* xr = fused ? h->xb[r & 1] : h->xb[0];
@@ -220,13 +220,13 @@ int shard_final_body(sfx_handle* h, const sfx_handle::Pending& p, int r_last, Ho
   } else {
     X = upd ? h->xb[0] : nullptr;
     int* Yw = h->xb[1];
-    if (upd) RC(shard_qmax(h, p.B, round_role(h, r_last), Yw));
+    if (upd) RC(shard_qmax(h, p.B, POST_ROLE, Yw));
     SselArgs S{};
     if (!upd || !can_fuse_v0(h, p.B + 1)) {
       S.role = R_A;
       S.row = 0;
     } else {
-      S.role = round_role(h, r_last);
+      S.role = POST_ROLE;
       S.row = p.B;
     }
     S.task = p.task;
@@ -370,7 +370,7 @@ int sfx_shard_td_maxima(sfx_t h, int round, int32_t* X) {
   if (!h || round < 0 || !X) SFX_FAIL(SFX_E_ARG, "bad args");
   RC(shard_fail_inactive(h));
   if (h->spend.B == 0) SFX_FAIL(SFX_E_STATE, "no minibatch in this step");
-  const int guess = round == 0 ? R_S1 : round_role(h, round - 1);
+  const int guess = round == 0 ? R_S1 : POST_ROLE;
   const GraphKey key = make_key(11, {h->spend.B, guess}, h->mask, {X});
   return run_graph(h, key, [&]() -> int { return run_qmax(h, guess, X); });
 }
@@ -381,8 +381,8 @@ int sfx_shard_td_update(sfx_t h, int round, const int32_t* X) {
   RC(shard_fail_inactive(h));
   const auto& P = h->spend;
   if (P.B == 0) SFX_FAIL(SFX_E_STATE, "no minibatch in this step");
-  const int out = round_role(h, round);
-  const GraphKey key = make_key(12, {P.B, round == 0 ? 1 : 0, out}, h->mask, {X, P.S, P.a, P.phi, P.S1, P.gamma, P.s_next});
+  const GraphKey key =
+      make_key(12, {P.B, round == 0 ? 1 : 0, POST_ROLE}, h->mask, {X, P.S, P.a, P.phi, P.S1, P.gamma, P.s_next});
   return run_graph(h, key, [&]() -> int {
     TdgSpec td;
     td.use_gpi = 1;
@@ -393,16 +393,16 @@ int sfx_shard_td_update(sfx_t h, int round, const int32_t* X) {
     BwdExtra bx;
     bx.inc_step = round == 0 ? 1 : 0;  // later rounds redo the same optimizer step
     bx.fuse_v0 = can_fuse_v0(h, P.B + 1);
-    bx.vRole = out;
+    bx.vRole = POST_ROLE;
     bx.v_x = P.S1;
     bx.v_xn = P.s_next;
     RC(run_bwd(h, 0, h->T, P.B, P.S, P.phi, nullptr, nullptr, td, bx));
     if (bx.fuse_v0) {
       FwdExtra vx;
       vx.l0 = 1;
-      return run_fwd(h, {{out, P_NEW, 0, 0, h->T}}, P.B + 1, nullptr, nullptr, vx);
+      return run_fwd(h, {{POST_ROLE, P_NEW, 0, 0, h->T}}, P.B + 1, nullptr, nullptr, vx);
     }
-    RC(run_fwd(h, {{out, P_NEW, 2, 0, h->T}}, P.B, P.S1, P.S1));
+    RC(run_fwd(h, {{POST_ROLE, P_NEW, 2, 0, h->T}}, P.B, P.S1, P.S1));
     return run_fwd(h, {{R_A, P_NEW, 1, 0, h->T}}, 1, P.s_next, nullptr);
   });
 }
@@ -412,9 +412,8 @@ int sfx_shard_ver_maxima(sfx_t h, int round, int32_t* Y) {
   if (!h || round < 0 || !Y) SFX_FAIL(SFX_E_ARG, "bad args");
   RC(shard_fail_inactive(h));
   if (h->spend.B == 0) SFX_FAIL(SFX_E_STATE, "no minibatch in this step");
-  const int post = round_role(h, round);
-  const GraphKey key = make_key(13, {h->spend.B, post}, h->mask, {Y});
-  return run_graph(h, key, [&]() -> int { return run_qmax(h, post, Y); });
+  const GraphKey key = make_key(13, {h->spend.B, POST_ROLE}, h->mask, {Y});
+  return run_graph(h, key, [&]() -> int { return run_qmax(h, POST_ROLE, Y); });
 }
 
 int sfx_shard_verify(sfx_t h, const int32_t* X, const int32_t* Y, int* flag) {
@@ -438,7 +437,7 @@ int sfx_shard_select(sfx_t h, int round, int task, int use_gpi, long long* key_o
     K.role = R_A;
     K.row = 0;
   } else if (can_fuse_v0(h, h->spend.B + 1)) {
-    K.role = round_role(h, round);
+    K.role = POST_ROLE;
     K.row = h->spend.B;
   } else {
     K.role = R_A;

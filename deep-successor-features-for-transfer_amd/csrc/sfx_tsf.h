@@ -1001,11 +1001,11 @@ __global__ __launch_bounds__(256) void k_bwd_tsf(Geo G, BwdArgs A, TsfArgs T, co
   bwd_body<BF>(G, A, A.head0, bx - ntsf, red);
 }
 
-// The ψ forward's first launch (layers 0 + 1 from the states, k_fwd<true, 8, true, BF>) with
+// The ψ forward's first launch (layers 0 + 1 from the states, k_fwd<true, true, BF>) with
 // k_tsf_fwd's workgroups riding along first in the same grid: the flow chains run beside the ψ
 // tiles.  (gx, gy) = the ψ launch's own grid; its workgroup r is (r % gx, r / gx % gy, r / gx gy).
 template <int NP, bool BF, int TP>
-__global__ __launch_bounds__(512) void k_fwd_tsf(Geo G, FwdArgs F, TsfArgs T, const float* __restrict__ gfl,
+__global__ __launch_bounds__(64 * FWD_WAVES) void k_fwd_tsf(Geo G, FwdArgs F, TsfArgs T, const float* __restrict__ gfl,
                                                   int ntsf, int gx, int gy) {
   __shared__ __attribute__((aligned(16))) float sm[TSFXF_SM];
   const int b = blockIdx.x;
@@ -1016,7 +1016,7 @@ __global__ __launch_bounds__(512) void k_fwd_tsf(Geo G, FwdArgs F, TsfArgs T, co
     return;
   }
   const int r = b - ntsf;
-  fwd_body<true, 8, true, BF, TP>(G, F, r % gx, (r / gx) % gy, r / (gx * gy));
+  fwd_body<true, true, BF, TP>(G, F, r % gx, (r / gx) % gy, r / (gx * gy));
 }
 
 // The one-state selection (k_sel1m: a workgroup per head, the last to arrive picks and publishes)

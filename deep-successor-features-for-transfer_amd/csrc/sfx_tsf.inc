@@ -150,7 +150,7 @@ int tsf_fwd_with(sfx_handle* h, int policy, int B, const float* S, const float* 
         grid.x = cdiv(F.ntN, 3);
       }
       launch(h, K_FWD, by + fwd_by, tsf_kernels(A.np).fride[h->bf16 ? 1 : 0][F.tpw - 1],
-             dim3(fgrid + grid.x * grid.y * grid.z), dim3(512), h->G, F, A, gfl, fgrid, (int)grid.x, (int)grid.y);
+             dim3(fgrid + grid.x * grid.y * grid.z), dim3(64 * FWD_WAVES), h->G, F, A, gfl, fgrid, (int)grid.x, (int)grid.y);
       rode = true;
       return true;
     };

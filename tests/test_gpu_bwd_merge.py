@@ -1,6 +1,6 @@
 """The merged last backward launch (run_bwd): the layer-0 dW tiles of the many-head
-callers compute their own 32 columns of dZ_0 -- the two dX tiles of layer 1 that a launch of its
-own used to run -- so a round has one backward launch fewer.
+callers, 16 columns wide, compute their own 16 columns of dZ_0 -- one dX tile of layer 1, which a
+launch of its own used to run -- so a round has one backward launch fewer.
 
 The tile does role_dx's arithmetic (same split of N over waves and lane groups, same MFMA k order,
 same wave-order reduction, same act_bwd), so everything must be IDENTICAL to SFX_BWD_MERGE=0, which
@@ -26,7 +26,8 @@ def _need_gpu():
 
 def run_loop(monkeypatch, merge, spec, T, B, n, ev=7, force=-1, precision=None, max_batch=None, record_oracle=False):
     """n native-runner steps (round skipping and look-ahead on, as by default; a target sync every
-    `ev` updates) on a handle created with SFX_BWD_MERGE=merge; everything a step leaves behind."""
+    `ev` updates) on a handle created with SFX_BWD_MERGE=merge; everything a step leaves behind, and
+    the engine's skip statistics as they stood when the run closed it."""
     from sfx.runner import NativeEnvLoop
 
     monkeypatch.setenv("SFX_BWD_MERGE", merge)
@@ -50,6 +51,7 @@ def run_loop(monkeypatch, merge, spec, T, B, n, ev=7, force=-1, precision=None, 
                moms=[eng.get_adam(t) for t in range(T)],
                actions=[(r["c"], r["a_greedy"]) for r in recs], final=final, stats=loop.stats())
     loop.close()
+    out["skips"] = eng.skip_stats()
     eng.close()
     return out
 

@@ -13,7 +13,6 @@ of a policy that skips the round (role_v0_only), which share the tile index spac
 import pytest
 
 from oracle import ref_cpu as R
-from tests import test_gpu_bwd_merge as M
 from tests.conftest import gpu_available
 from tests.test_gpu_bwd_merge import assert_identical, bwd_launches, run_loop
 
@@ -52,34 +51,12 @@ CASES = {
 SKIPS = ("odd-tiles-h48", "ragged-h24-b7")
 
 
-def run_loop_skips(monkeypatch, merge, spec, T, B, n, **kw):
-    """run_loop, plus the engine's skip statistics as they stood when the run closed it."""
-    seen, make_engine = {}, M.make
-
-    def make(*a, **k):
-        eng, st = make_engine(*a, **k)
-        close = eng.close
-
-        def close_keeping_stats():
-            seen.update(eng.skip_stats())
-            close()
-
-        eng.close = close_keeping_stats
-        return eng, st
-
-    with monkeypatch.context() as mp:
-        mp.setattr(M, "make", make)
-        out = run_loop(mp, merge, spec, T, B, n, **kw)
-    out["skips"] = seen
-    return out
-
-
 @pytest.mark.parametrize("case", list(CASES), ids=list(CASES))
 def test_mg16_is_bit_exact(case, monkeypatch):
     c = dict(CASES[case])
     spec, T, B = c.pop("spec"), c.pop("T"), c.pop("B")
-    on = run_loop_skips(monkeypatch, "1", spec, T, B, 30, **c)
-    off = run_loop_skips(monkeypatch, "0", spec, T, B, 30, **c)
+    on = run_loop(monkeypatch, "1", spec, T, B, 30, **c)
+    off = run_loop(monkeypatch, "0", spec, T, B, 30, **c)
     print(case, "skips on/off", on["skips"], off["skips"], on["stats"])
     assert_identical(on, off)
     if "force" in c:
