@@ -495,3 +495,128 @@ int sfx_phi_test_update(sfx_t h, const float* s, const int64_t* a, float r, cons
 }
 
 }  // extern "C"
+
+// ---- SF-φ's test tasks in lockstep: E rows per launch set ------------------------------------
+
+namespace {
+
+int phi_rows_ok(sfx_handle* h, int E, const char* name) {
+  RC(phi_test_ok(h, false, name));
+  if (E < 1 || E > PHIE || E > h->Mmax)
+    SFX_FAIL(SFX_E_ARG, std::string(name) + ": E must be in [1, min(" + std::to_string(PHIE) + ", max_batch)]");
+  return SFX_OK;
+}
+
+// φ of E rows into out [E][d], row e bit for bit phi_features_impl's one-row result
+int phi_rows_impl(sfx_handle* h, const float* S, const int64_t* a, const float* S1, int E, float* out) {
+  sfx_phi_state* s = h->phi;
+  if (!s->wide) {
+    PhiArgs A = phi_args(h, 0, 1);
+    A.S = S;
+    A.S1 = S1;
+    A.a = a;
+    A.phis = out;
+    launch(h, K_TSF, 4.0 * E * (s->P + (double)s->n_in + h->d), k_phiE_narrow, dim3(E), dim3(256), A);
+    LAUNCHCHK();
+    return SFX_OK;
+  }
+  const int L = s->n_mid + 2;
+  size_t off = 0;
+  for (int l = 0; l < L; ++l) {
+    PhiEArgs A{};
+    A.K = l == 0 ? s->n_in : s->hid;
+    A.N = l == L - 1 ? h->d : s->hid;
+    A.W = s->p + off;
+    off += (size_t)A.N * (A.K + 1);
+    A.X = l == 0 ? nullptr : s->acts + (size_t)(l - 1) * E * s->hid;
+    A.Y = l == L - 1 ? out : s->acts + (size_t)l * E * s->hid;
+    A.S = S;
+    A.S1 = S1;
+    A.a = a;
+    A.n_s = h->n_s;
+    A.relu = l < L - 1;
+    A.E = E;
+    const double bytes = 4.0 * ((double)A.N * (A.K + 1) + (double)E * (A.K + A.N));
+    const dim3 grid(cdiv(A.N, PHI1_R)), block(64 * PHI1_R * PHI1_S);
+    // k_phi1_fwd's test for 16-byte words (its x, s->acts + (l - 1) hid, is aligned when K = hid is a multiple
+    // of 4, as this one): then the rows go through LDS, PHIE_LDS of them per launch; else the scalar-load kernel
+    const bool vec = A.X && (A.K & 3) == 0 && A.K <= PHIW_HID && (((uintptr_t)A.W | (uintptr_t)A.X) & 15) == 0;
+    if (vec) {
+      const dim3 gl(cdiv(A.N, PHI1_R * PHIE_G));
+      for (int e0 = 0; e0 < E; e0 += PHIE_LDS) {
+        PhiEArgs C = A;
+        C.E = std::min(PHIE_LDS, E - e0);
+        C.X = A.X + (size_t)e0 * A.K;
+        C.Y = A.Y + (size_t)e0 * A.N;
+        const double by = 4.0 * ((double)A.N * (A.K + 1) + (double)C.E * (A.K + A.N));
+        if (C.E == 1)
+          launch(h, K_TSF, by, k_phiE_fwd_lds<1>, gl, block, C);
+        else if (C.E == 2)
+          launch(h, K_TSF, by, k_phiE_fwd_lds<2>, gl, block, C);
+        else if (C.E <= 4)
+          launch(h, K_TSF, by, k_phiE_fwd_lds<4>, gl, block, C);
+        else
+          launch(h, K_TSF, by, k_phiE_fwd_lds<PHIE_LDS>, gl, block, C);
+        LAUNCHCHK();
+      }
+      continue;
+    }
+    if (E == 1)
+      launch(h, K_TSF, bytes, k_phiE_fwd<1>, grid, block, A);
+    else if (E == 2)
+      launch(h, K_TSF, bytes, k_phiE_fwd<2>, grid, block, A);
+    else if (E <= 4)
+      launch(h, K_TSF, bytes, k_phiE_fwd<4>, grid, block, A);
+    else if (E <= 8)
+      launch(h, K_TSF, bytes, k_phiE_fwd<8>, grid, block, A);
+    else
+      launch(h, K_TSF, bytes, k_phiE_fwd<PHIE>, grid, block, A);
+    LAUNCHCHK();
+  }
+  return SFX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sfx_phi_features_rows(sfx_t h, const float* S, const int64_t* a, const float* S1, int E, float* phi) {
+  RC(settle(h));
+  RC(phi_rows_ok(h, E, "sfx_phi_features_rows"));
+  if (!S || !a || !S1 || !phi) SFX_FAIL(SFX_E_ARG, "sfx_phi_features_rows: null argument");
+  return phi_rows_impl(h, S, a, S1, E, phi);
+}
+
+int sfx_phi_test_actions(sfx_t h, const float* S, int E, const float* W, int w_stride, const float* Wb, float* q,
+                         int64_t* out) {
+  RC(settle(h));
+  RC(phi_rows_ok(h, E, "sfx_phi_test_actions"));
+  if (!S || !W || !Wb || !out) SFX_FAIL(SFX_E_ARG, "sfx_phi_test_actions: null argument");
+  if (w_stride < h->d) SFX_FAIL(SFX_E_ARG, "sfx_phi_test_actions: w_stride must be at least d");
+  RC(run_fwd(h, {{R_G, P_ONLINE, 1, 0, h->T}}, E, S, nullptr));
+  GpiArgs g = gpi_args(R_G, 0, 0, W, nullptr, q, nullptr, nullptr, out, 0, 1, E);
+  g.w_stride = w_stride;
+  g.sel_stride = 2;
+  launch(h, K_GPI, 4.0 * E * ((double)h->T * h->O + h->d + 1.0 + (q ? h->T * h->A : 0)), k_phi_test_act, dim3(E),
+         dim3(256), h->G, g, Wb);
+  LAUNCHCHK();
+  return SFX_OK;
+}
+
+int sfx_phi_test_updates(sfx_t h, int E, const float* S, const int64_t* a, const float* r, const float* S1, float* W,
+                         int w_stride, float* Wb, float* loss) {
+  RC(settle(h));
+  RC(phi_rows_ok(h, E, "sfx_phi_test_updates"));
+  if (!S || !a || !r || !S1 || !W || !Wb || !loss) SFX_FAIL(SFX_E_ARG, "sfx_phi_test_updates: null argument");
+  if (w_stride < h->d) SFX_FAIL(SFX_E_ARG, "sfx_phi_test_updates: w_stride must be at least d");
+  RC(phi_rows_impl(h, S, a, S1, E, h->phi->phis));
+  PhiTestArgs A = phi_test_args(h);
+  A.w = W;
+  A.wb = Wb;
+  A.losses = loss;
+  launch(h, K_TSF, 4.0 * E * (3.0 * h->d + 4.0), k_phi_test_steps, dim3(E), dim3(64), A, r, w_stride);
+  LAUNCHCHK();
+  return SFX_OK;
+}
+
+}  // extern "C"

@@ -34,6 +34,20 @@
 //     W, β, w, b_w, ascent on λ), λ clamped to [1e-2, 1e6] (:502).  ψ, ψ⁻, g_t, h and the φ net are read only.
 //   k_phi_test_step     SF-φ: ρ = w·φ + b_w - r, loss = ρ², ∂w = 2ρ φ, ∂b_w = 2ρ, the same clamp and step.
 //
+// SF-φ's test tasks in lockstep (agents/sfdqn_phi.py:211-212 over test_agent :234-261; sfx/lockstep.py
+// test_tasks_lockstep_phi): E <= PHIE rows per launch, every row bit for bit what the one-row call gives.
+//   k_phiE_fwd        k_phi1_fwd for E rows: the same split of k over lanes and waves, the same fmaf chain,
+//                     butterfly and wave-order add, E accumulators per lane.  A trip's words of W are loaded
+//                     once and held in registers.  Rows in 16-byte words: k_phiE_fwd_lds, the E <= 8 input rows
+//                     staged once per workgroup in LDS (64 KB at E = 8, K = 2048), two row groups of W per
+//                     workgroup.  Scalar loads (layer 0, an odd hid): k_phiE_fwd, the rows read from L2 per use.
+//                     k_phiE_narrow: the narrow net, a workgroup per row.
+//                     Measured (hid 2048): 30.9 / 37.6 / 51.9 / 81.5 µs at E = 1 / 2 / 4 / 8,
+//                     3.4× faster than 8 one-row chains, 1.8× slower than the MFMA forward at B = 8 (whose
+//                     sums differ in the last bits).
+//   k_phi_test_steps  k_phi_test_step for E rows, one wave per row, r read from the device.
+//   k_phi_test_act    the E greedy actions under q = fl(ψ·w + b_w): the bias added after the dot product.
+//
 // One workgroup each: the step is 2 (A + 1) products of the d × T d matrix and one pass over it, 588 entries
 // at the reference's T = 4, d = 12, A = 9 -- launch latency, not work.  Limits (LDS): d <= 64, A <= 64,
 // A d <= 1024, T d <= 1024, A T d <= 4096 (x_a and y_a of every action are held, 32 KB).
@@ -42,6 +56,7 @@
 namespace sfx {
 
 constexpr int PHI1_R = 2, PHI1_S = 2;  // rows of W per workgroup, waves per row
+constexpr int PHIE = 16;               // test tasks (input rows) per launch of the lockstep kernels
 constexpr int PHIT_D = 64, PHIT_A = 64, PHIT_AD = 1024, PHIT_TD = 1024, PHIT_ATD = 4096;
 
 struct Phi1Args {
@@ -301,8 +316,8 @@ __global__ __launch_bounds__(256) void k_tsfphi_test_step(PhiTestArgs A) {
   }
 }
 
-// SFDQN_PHI.update_test_reward_mapper after φ: one wave
-__global__ __launch_bounds__(64) void k_phi_test_step(PhiTestArgs A) {
+// SFDQN_PHI.update_test_reward_mapper after φ: one wave (the body of k_phi_test_step and k_phi_test_steps)
+__device__ __forceinline__ void phi_test_step_row(const PhiTestArgs& A) {
   __shared__ float s_rho;
   const int tid = threadIdx.x, d = A.d;
   const AdamC c1 = adam_consts(A.hpa, 1);
@@ -319,6 +334,242 @@ __global__ __launch_bounds__(64) void k_phi_test_step(PhiTestArgs A) {
   const float rho2 = __fmul_rn(2.f, s_rho);
   if (tid < d) A.w[tid] = fresh_adam(wk, phit_clamp(__fmul_rn(rho2, pk)), c1);
   if (tid == 0) *A.wb = fresh_adam(wb, phit_clamp(rho2), c1);
+}
+
+__global__ __launch_bounds__(64) void k_phi_test_step(PhiTestArgs A) { phi_test_step_row(A); }
+
+// ---- E test tasks in lockstep (sfx.lockstep.test_tasks_lockstep_phi) ---------------------------
+
+// E rows of one Linear (+ ReLU) of the wide φ net; Y[e][o] is bit for bit what k_phi1_fwd writes for row e
+struct PhiEArgs {
+  const float* W;   // [N][K], bias [N] right after
+  const float* X;   // [E][K] the layer's input; nullptr: layer 0, x_e = S[e] ⊕ a[e] ⊕ S1[e]
+  float* Y;         // [E][N]
+  const float* S;   // [E][n_s]
+  const float* S1;
+  const int64_t* a; // [E]
+  int K, N, n_s, relu, E;
+};
+
+__device__ __forceinline__ float phiE_x(const PhiEArgs& A, int e, int k) {
+  if (A.X) return A.X[(long long)e * A.K + k];
+  const long long r = (long long)e * A.n_s;
+  return k < A.n_s ? A.S[r + k] : (k == A.n_s ? (float)A.a[e] : A.S1[r + k - A.n_s - 1]);
+}
+
+// k_phi1_fwd's scalar-load path for E rows (a row of W or x that is not in 16-byte words: layer 0 always, an
+// odd hid; phi_rows_impl sends every other layer to k_phiE_fwd_lds).  The input rows are read per use.
+// EB: the accumulators a lane holds, E <= EB; the slots past E recompute row E - 1 and are dropped
+template <int EB>
+__global__ __launch_bounds__(64 * PHI1_R * PHI1_S) void k_phiE_fwd(PhiEArgs A) {
+  __shared__ float part[PHI1_R][PHI1_S][EB];
+  const int tid = threadIdx.x, wv = tid >> 6, l = tid & 63, rr = wv / PHI1_S, q = wv - rr * PHI1_S;
+  const int K = A.K, N = A.N, E = A.E;
+  const int o = blockIdx.x * PHI1_R + rr;
+  float acc[EB];
+#pragma unroll
+  for (int e = 0; e < EB; ++e) acc[e] = 0.f;
+  if (o < N) {
+    const float* wrow = A.W + (long long)o * K;
+    const int kq = (K + PHI1_S - 1) / PHI1_S;
+    const int beg = q * kq, end = min(K, beg + kq);
+    for (int b = beg; b < end; b += 256) {
+      float w[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int k = b + 64 * u + l;
+        w[u] = k < end ? wrow[k] : 0.f;
+      }
+#pragma unroll
+      for (int e = 0; e < EB; ++e) {
+        const int er = min(e, E - 1);
+        float x[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const int k = b + 64 * u + l;
+          x[u] = k < end ? phiE_x(A, er, k) : 0.f;
+        }
+        float v = acc[e];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) v = __builtin_fmaf(w[u], x[u], v);
+        acc[e] = v;
+      }
+    }
+  }
+#pragma unroll
+  for (int e = 0; e < EB; ++e) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) acc[e] = __fadd_rn(acc[e], __shfl_xor(acc[e], m, 64));
+    if (l == 0) part[rr][q][e] = acc[e];
+  }
+  __syncthreads();
+  if (q == 0 && l < E && o < N) {  // lane e finishes row e
+    float v = part[rr][0][l];
+#pragma unroll
+    for (int j = 1; j < PHI1_S; ++j) v = __fadd_rn(v, part[rr][j][l]);
+    v = __fadd_rn(v, A.W[(long long)N * K + o]);
+    A.Y[(long long)l * N + o] = A.relu ? fmaxf(v, 0.f) : v;
+  }
+}
+
+// k_phiE_fwd's 16-byte-word path with the E <= EB <= PHIE_LDS input rows staged once per workgroup in LDS
+// (K <= PHIW_HID: 8 KB a row) and PHIE_G row groups of W per workgroup, so the rows are fetched from L2 once per
+// 2 PHIE_G rows of W instead of once per wave.  The first trip's words of W of every row group are requested
+// before the staging, so they are in flight while it runs.  Per row of W the same lanes, waves and fmaf order.
+constexpr int PHIE_G = 2, PHIE_LDS = 8;
+
+template <int EB>  // 2 waves per SIMD: the grid is 2 workgroups per CU on a 2048-wide layer, and 64 KB of LDS allow no more
+__global__ __launch_bounds__(64 * PHI1_R * PHI1_S, 2) void k_phiE_fwd_lds(PhiEArgs A) {
+  static_assert(EB <= PHIE_LDS, "LDS holds PHIE_LDS rows");
+  __shared__ float4 xs[EB * (PHIW_HID / 4)];
+  __shared__ float part[PHIE_G][PHI1_R][PHI1_S][EB];
+  const int tid = threadIdx.x, wv = tid >> 6, l = tid & 63, rr = wv / PHI1_S, q = wv - rr * PHI1_S;
+  const int K = A.K, N = A.N, E = A.E;
+  const int K4 = K >> 2, q4 = (K4 + PHI1_S - 1) / PHI1_S;
+  const int beg = q * q4, end = min(K4, beg + q4);
+  const float4* x4 = reinterpret_cast<const float4*>(A.X);
+  const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+  float4 w0[PHIE_G][4];
+#pragma unroll
+  for (int g = 0; g < PHIE_G; ++g) {
+    const int o = (blockIdx.x * PHIE_G + g) * PHI1_R + rr;
+    const float4* w4 = reinterpret_cast<const float4*>(A.W + (long long)min(o, N - 1) * K);
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int i = beg + 64 * u + l;
+      w0[g][u] = (o < N && i < end) ? w4[i] : z4;
+    }
+  }
+  for (int i = tid; i < E * K4; i += 64 * PHI1_R * PHI1_S) xs[i] = x4[i];
+  __syncthreads();
+  float acc[PHIE_G][EB];
+#pragma unroll
+  for (int g = 0; g < PHIE_G; ++g) {
+#pragma unroll
+    for (int e = 0; e < EB; ++e) acc[g][e] = 0.f;
+    const int o = (blockIdx.x * PHIE_G + g) * PHI1_R + rr;
+    if (o < N) {
+      const float4* w4 = reinterpret_cast<const float4*>(A.W + (long long)o * K);
+      for (int b = beg; b < end; b += 256) {
+        float4 w[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const int i = b + 64 * u + l;
+          w[u] = b == beg ? w0[g][u] : (i < end ? w4[i] : z4);
+        }
+#pragma unroll
+        for (int e = 0; e < EB; ++e) {
+          const float4* xe = xs + min(e, E - 1) * K4;
+          float4 x[4];
+#pragma unroll
+          for (int u = 0; u < 4; ++u) {
+            const int i = b + 64 * u + l;
+            x[u] = i < end ? xe[i] : z4;
+          }
+          float v = acc[g][e];
+#pragma unroll
+          for (int u = 0; u < 4; ++u) {
+            v = __builtin_fmaf(w[u].x, x[u].x, v);
+            v = __builtin_fmaf(w[u].y, x[u].y, v);
+            v = __builtin_fmaf(w[u].z, x[u].z, v);
+            v = __builtin_fmaf(w[u].w, x[u].w, v);
+          }
+          acc[g][e] = v;
+        }
+      }
+    }
+#pragma unroll
+    for (int e = 0; e < EB; ++e) {
+#pragma unroll
+      for (int m = 32; m >= 1; m >>= 1) acc[g][e] = __fadd_rn(acc[g][e], __shfl_xor(acc[g][e], m, 64));
+      if (l == 0) part[g][rr][q][e] = acc[g][e];
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int g = 0; g < PHIE_G; ++g) {
+    const int o = (blockIdx.x * PHIE_G + g) * PHI1_R + rr;
+    if (q == 0 && l < E && o < N) {  // lane e finishes row e
+      float v = part[g][rr][0][l];
+#pragma unroll
+      for (int j = 1; j < PHI1_S; ++j) v = __fadd_rn(v, part[g][rr][j][l]);
+      v = __fadd_rn(v, A.W[(long long)N * K + o]);
+      A.Y[(long long)l * N + o] = A.relu ? fmaxf(v, 0.f) : v;
+    }
+  }
+}
+
+// A narrow net (hid <= PHI_HID): k_phi_fwd's computation of one row (the fmaf chain over k, the bias, the
+// ReLU), one workgroup per row, the activations in LDS only.
+__global__ __launch_bounds__(256) void k_phiE_narrow(PhiArgs A) {
+  __shared__ float sx[PHI_HID], sy[PHI_HID];
+  const int tid = threadIdx.x, e = blockIdx.x, n_s = A.n_s, L = A.n_mid + 2;
+  for (int k = tid; k < A.n_in; k += 256)
+    sx[k] = k < n_s ? A.S[(long long)e * n_s + k]
+                    : (k == n_s ? (float)A.a[e] : A.S1[(long long)e * n_s + (k - n_s - 1)]);
+  __syncthreads();
+  float* x = sx;
+  float* y = sy;
+  for (int l = 0; l < L; ++l) {
+    const int K = phi_layer_in(A, l), N = phi_layer_out(A, l);
+    const float* W = A.p + phi_layer_off(A, l);
+    const float* bias = W + (long long)N * K;
+    for (int o = tid; o < N; o += 256) {
+      float acc = 0.f;
+      for (int k = 0; k < K; ++k) acc = __builtin_fmaf(x[k], W[(long long)o * K + k], acc);
+      acc = __fadd_rn(acc, bias[o]);
+      if (l == L - 1)
+        A.phis[(long long)e * N + o] = acc;
+      else
+        y[o] = fmaxf(acc, 0.f);
+    }
+    __syncthreads();
+    float* t = x;
+    x = y;
+    y = t;
+  }
+}
+
+// E updates of k_phi_test_step in one launch, one wave (workgroup) per row: row e's w at w + e w_stride, its
+// bias at wb + e, φ_e at phi + e d, r_e read from the device, loss_e to losses + e.
+__global__ __launch_bounds__(64) void k_phi_test_steps(PhiTestArgs A, const float* r, int w_stride) {
+  const int e = blockIdx.x;
+  A.w += (long long)e * w_stride;
+  A.wb += e;
+  A.phi += (long long)e * A.d;
+  A.r = r[e];
+  A.losses += e;
+  phi_test_step_row(A);
+}
+
+// SFDQN_PHI.get_test_action's greedy branch for E test tasks (agents/sfdqn_phi.py:223-232 over
+// features/deep_phi.py GPI_w): k_gpi's row with the reward model's bias added AFTER the dot product,
+// q[e,t,a] = fl(ψ_t(S[e])[a,:]·W[e,:] + Wb[e]), then the first-index argmaxes.  One workgroup per row.
+__global__ __launch_bounds__(256) void k_phi_test_act(Geo G, GpiArgs A, const float* Wb) {
+  __shared__ float s_q[QMAX];
+  __shared__ float s_w[DMAX];
+  __shared__ float s_mt[256], s_ma[256];
+  const int tid = threadIdx.x, b = blockIdx.x;
+  const int T = G.T, Aa = G.A, d = G.d, O = G.O, NLm = G.lastOff, TA = T * Aa;
+  const long long ob = (long long)(A.row0 + b);
+  const int lb = A.rowoff + b;
+  const float* wr = A.w + ob * A.w_stride;
+  const float wb = Wb[ob];
+  int64_t* so = A.sel_out + ob * A.sel_stride;
+  for (int k = tid; k < d; k += 256) s_w[k] = wr[k];
+  __syncthreads();
+  for (int idx = tid; idx < TA; idx += 256) {
+    const int t = idx / Aa, a = idx - t * Aa;
+    const float* p = G.actp(A.role, t, NLm) + (size_t)lb * O + a * d;
+    float q = 0.f;
+#pragma unroll 8
+    for (int k = 0; k < d; ++k) q = __builtin_fmaf(p[k], s_w[k], q);
+    q = __fadd_rn(q, wb);
+    s_q[idx] = q;
+    if (A.q_out) A.q_out[(ob * T + t) * Aa + a] = q;
+  }
+  __syncthreads();
+  gpi_pick(A, s_q, s_mt, s_ma, T, Aa, ob, so, 256);
 }
 
 }  // namespace sfx

@@ -134,6 +134,9 @@ SIGNATURES = {
     "sfx_tsf_phi_test_action": (_I, [_VP] * 7),
     "sfx_tsf_phi_test_update": (_I, [_VP, _VP, _VP, _F, _VP, _F] + [_VP] * 6),
     "sfx_phi_test_update": (_I, [_VP, _VP, _VP, _F, _VP, _VP, _VP, _VP]),
+    "sfx_phi_test_actions": (_I, [_VP, _VP, _I, _VP, _I, _VP, _VP, _VP]),
+    "sfx_phi_test_updates": (_I, [_VP, _I, _VP, _VP, _VP, _VP, _VP, _I, _VP, _VP]),
+    "sfx_phi_features_rows": (_I, [_VP, _VP, _VP, _VP, _I, _VP]),
     "sfx_tsf_test_update": (_I, [_VP, _VP, _VP, _VP, _VP, _F, _VP, _VP, _VP, _VP, _I] + [_F] * 7 + [_VP]),
     "sfx_tsf_test_actions": (_I, [_VP, _VP, _I, _VP, _I, _VP, _I, _VP]),
     "sfx_tsf_test_updates": (_I, [_VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, _I, _VP, _I, _VP, _I, _VP, _F, _F, _F, _VP]),

@@ -774,6 +774,70 @@ class SFEngine:
               "sfx_phi_test_update")
         return loss
 
+    # ---------------------------------------------------------------- SF-φ test tasks in lockstep
+    PHI_ROWS = 16  # csrc/sfx_phitest.h PHIE: test tasks per launch set
+
+    def _phi_rows(self, s, a, s1, r=None):
+        t = self._h2d_many([(s, torch.float32), (s1, torch.float32), (a, torch.long)]
+                           + ([] if r is None else [(r, torch.float32)]))
+        s, s1 = t[0].reshape(-1, self.n_s).contiguous(), t[1].reshape(-1, self.n_s).contiguous()
+        a = t[2].reshape(-1).contiguous()
+        E = s.shape[0]
+        if s1.shape[0] != E or a.numel() != E or (r is not None and t[3].numel() != E):
+            raise ValueError("s, a, s1 (and r) must have the same number of rows")
+        return (s, a, s1) if r is None else (s, a, s1, t[3].reshape(-1).contiguous())
+
+    def _phi_w_rows(self, W, Wb, E):
+        if not (torch.is_tensor(W) and W.dim() == 2 and W.shape == (E, self.d) and W.stride(1) == 1
+                and W.dtype == torch.float32 and W.device == self.device and W.stride(0) >= self.d):
+            raise ValueError(f"W must be a float32 [{E}, {self.d}] device tensor with unit column stride")
+        if Wb.numel() != E:
+            raise ValueError(f"Wb must hold {E} floats")
+        return W.data_ptr(), W.stride(0), _dev_f32(Wb, self.device)
+
+    def phi_features_rows(self, s, a, s1, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """φ of E <= PHI_ROWS rows, s / s1 [E, n_s], a [E] -> [E, d]: row e is bit for bit
+        ``phi_features(s[e], a[e:e+1], s1[e])``, the φ net streamed once for all rows."""
+        s, a, s1 = self._phi_rows(s, a, s1)
+        E = s.shape[0]
+        out = torch.empty(E, self.d, device=self.device) if out is None else out
+        check(lib.sfx_phi_features_rows(self._h, s.data_ptr(), a.data_ptr(), s1.data_ptr(), E,
+                                        _dev_f32(out, self.device)), "sfx_phi_features_rows")
+        return out
+
+    def phi_test_actions(self, S, W: torch.Tensor, Wb: torch.Tensor, q_out: Optional[torch.Tensor] = None):
+        """SFDQN_PHI.get_test_action's greedy branch (agents/sfdqn_phi.py:223-232) of E test tasks in one launch
+        set, row e under its own Linear(d, 1): W [E, d] / Wb [E] float32 device tensors.  q = ψ·w + b with the
+        bias added after the dot product, as DeepSF_PHI.GPI_w adds it.  Returns the device tensor [E, 2] of
+        (c, a) (not synchronized)."""
+        S = self._f(S)
+        if S.dim() == 1:
+            S = S.reshape(1, -1)
+        E = S.shape[0]
+        w_ptr, w_stride, wb_ptr = self._phi_w_rows(W, Wb, E)
+        if q_out is not None:
+            _dev_f32(q_out, self.device)
+        out = torch.empty(E, 2, dtype=torch.long, device=self.device)
+        check(lib.sfx_phi_test_actions(self._h, S.data_ptr(), E, w_ptr, w_stride, wb_ptr, dptr(q_out),
+                                       out.data_ptr()), "sfx_phi_test_actions")
+        return out
+
+    def phi_test_updates(self, s, a, r, s1, W: torch.Tensor, Wb: torch.Tensor,
+                         losses: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """SFDQN_PHI.update_test_reward_mapper (agents/sfdqn_phi.py:263-305) of E test tasks in one launch set:
+        row e as ``phi_test_update(s[e], a[e], r[e], s1[e], W[e], Wb[e:e+1])``, bit for bit.  W [E, d] and
+        Wb [E] (float32 device tensors) are updated in place; returns the E losses (device, not synchronized)."""
+        s, a, s1, r = self._phi_rows(s, a, s1, r)
+        E = s.shape[0]
+        w_ptr, w_stride, wb_ptr = self._phi_w_rows(W, Wb, E)
+        losses = torch.empty(E, device=self.device) if losses is None else losses
+        _dev_f32(losses, self.device)
+        if losses.numel() != E:
+            raise ValueError(f"losses must hold {E} floats")
+        check(lib.sfx_phi_test_updates(self._h, E, s.data_ptr(), a.data_ptr(), r.data_ptr(), s1.data_ptr(), w_ptr,
+                                       w_stride, wb_ptr, losses.data_ptr()), "sfx_phi_test_updates")
+        return losses
+
     # ---------------------------------------------------------------- TSF test tasks
     def tsf_test_action(self, s, w: torch.Tensor, omega: torch.Tensor, out: Optional[torch.Tensor] = None):
         """TSFDQN.get_test_action's greedy branch (tsfdqn.py:859-870): a 0-d int64 device tensor.

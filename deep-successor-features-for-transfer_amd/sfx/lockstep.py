@@ -47,6 +47,13 @@ TSF phase: the same lines as the sequential loop over the bound reward mapper
 block to one line), but a step's lines are printed for all live tasks together, so across tasks
 their order interleaves where the sequential loop prints task by task; the SF phase prints in the
 reference's order.
+
+The learned-φ SF agent's test phase (agents/sfdqn_phi.py:211-212 over test_agent :234-261) runs in
+lockstep as well (``test_tasks_lockstep_phi``): its φ net and ψ heads are read only, each test task owns
+its biased ``w_approx`` and the reward mapper builds a fresh Adam per step.  Here φ feeds ``w`` through
+Adam and ``w`` picks the next action, so the E-row kernels reproduce the one-row calls bit for bit
+(csrc/sfx_phitest.h) and the phase follows the sequential trajectory exactly.  TSF-φ stays sequential: all
+its test tasks write the one shared Ω.
 """
 from __future__ import annotations
 
@@ -357,6 +364,115 @@ def _tsf_group(agent, eng, test_tasks, entries, omegas, sched, idx):
     return R, [[Lh[j][e] for j in range(steps[e])] for e in range(E)]
 
 
+def phi_agent(agent) -> bool:
+    """``agent`` is an SFDQN_PHI over sfx's DeepSF_PHI (agents/sfdqn_phi.py: biased reward models, no shared
+    Ω), whose test phase ``test_tasks_lockstep_phi`` runs.  Told by the library alone: the agent gets its φ net
+    (``agent.phi``) only in ``add_training_task`` (:136), inside ``train``."""
+    return (not hasattr(agent, "omegas")
+            and callable(getattr(getattr(agent, "sf", None), "phi_test_supported", None)))
+
+
+def test_tasks_lockstep_phi(agent, test_tasks: Sequence, indices: Sequence[int] = None, *, episodes_end=None,
+                            sequential=None) -> List:
+    """``[agent.test_agent(task, i) for i, task in enumerate(test_tasks)]`` of agents/sfdqn_phi.py (:211-212 over
+    test_agent :234-261) with the episodes in lockstep.  ``agent`` is the user's SFDQN_PHI over sfx's drop-in
+    DeepSF_PHI; ``agent.test_tasks_weights[i]`` the test task's nn.Linear(d, 1) with bias, updated in place.
+
+    The ψ heads and the φ net are read only in the test phase, each test task owns its env and its reward
+    model, and the reward mapper builds a fresh Adam per step, so the E episodes are independent but for
+    Python's ``random`` stream (:226-227, drawn as agents/sfdqn.py draws: taken up front).  Per step: one
+    ``sfx_phi_test_actions`` launch set and one read of the E greedy actions, the E env steps, one
+    ``sfx_phi_test_updates`` launch set (the φ net streamed once for the E transitions) on device copies of
+    the E (weight, bias) rows.  Every row of both is bit for bit the one-row call's result, so the actions,
+    returns, reward models, log lines and the random state are the sequential loop's.  The losses stay on the
+    device and are read once per group; more than the engine's ``PHI_ROWS`` test tasks run as consecutive groups.
+
+    Lockstep runs only when ``fixed_horizon(test_tasks, episodes_end)`` holds and the library takes every
+    reward model and the φ net (``sf.phi_test_supported``); otherwise the sequential loop (``sequential``,
+    default ``agent.test_agent``) runs."""
+    E = len(test_tasks)
+    if E == 0:
+        return []
+    idx = list(range(E)) if indices is None else list(indices)
+    sf = agent.sf
+    ws = [agent.test_tasks_weights[i] for i in idx]
+    phi_model = agent.phi[0][0]
+    if not fixed_horizon(test_tasks, episodes_end) or not all(sf.phi_test_supported(phi_model, w) for w in ws):
+        seq = sequential or agent.test_agent
+        return [seq(task, i) for i, task in zip(idx, test_tasks)]
+    eng = sf._phi_engine(phi_model, 1)  # loads the φ net on first use, as the bound update_test_reward_mapper
+    sf._flush()
+    T = int(agent.T)
+    sched = _draw_schedule(E, T, float(agent.test_epsilon), int(agent.n_actions))
+    cap = max(1, min(int(eng.PHI_ROWS), int(eng.max_batch)))
+    R, acc = [], []
+    for e0 in range(0, E, cap):
+        sl = slice(e0, min(E, e0 + cap))
+        r_, a_ = _phi_group(agent, eng, test_tasks[sl], ws[sl], sched[sl], idx[sl])
+        R += r_
+        acc += a_
+    for e in range(E):
+        agent.logger.log_target_error_progress(agent.get_target_reward_mapper_error(R[e], acc[e], idx[e], T))
+    return R
+
+
+def _phi_group(agent, eng, test_tasks, ws, sched, idx):
+    """One lockstep group of E <= eng.PHI_ROWS SF-φ test tasks: (returns, accumulated losses)."""
+    sf, E, T = agent.sf, len(test_tasks), int(agent.T)
+    dev = eng.device
+    adev = getattr(agent, "device", None) or sf._out_device()
+    W = torch.cat([w.weight.detach().to(dev, torch.float32).reshape(1, -1) for w in ws]).contiguous()
+    Wb = torch.cat([w.bias.detach().to(dev, torch.float32).reshape(1) for w in ws]).contiguous()
+    L = torch.zeros(T, E, device=dev)
+    row = lambda x: torch.as_tensor(x).to(dev, torch.float32).reshape(1, -1)  # noqa: E731
+    s_enc = [agent.encoding(task.initialize()) for task in test_tasks]
+    R = [0.0] * E
+    steps = [0] * E
+    live = list(range(E))  # all of them unless a declared-endless episode ends
+    for j in range(T):
+        part = len(live) < E
+        rows = torch.tensor(live, device=dev) if part else None
+        Wl, Wbl = (W[rows].contiguous(), Wb[rows].contiguous()) if part else (W, Wb)
+        S = torch.cat([row(s_enc[e]) for e in live])
+        greedy = eng.phi_test_actions(S, Wl, Wbl)[:, 1]
+        picked = greedy.tolist()  # the step's one read of the E actions
+        greedy = greedy.to(adev).unbind()
+        acts, rs, s1_enc, ended = [], [], [], []
+        for k, e in enumerate(live):
+            x = sched[e][j]
+            a = torch.tensor(x).to(adev) if x >= 0 else greedy[k]
+            s1, r, done = test_tasks[e].transition(a)
+            s1_enc.append(agent.encoding(s1))
+            acts.append(x if x >= 0 else picked[k])
+            rs.append(float(r))
+            R[e] += r
+            steps[e] += 1
+            if done and j + 1 < T:
+                _warn_ended(idx[e], j + 1, T)
+                ended.append(e)
+        Lj = eng.phi_test_updates(S, torch.tensor(acts, dtype=torch.long), torch.tensor(rs, dtype=torch.float32),
+                                  torch.cat([row(x) for x in s1_enc]), Wl, Wbl, losses=None if part else L[j])
+        if part:
+            W[rows], Wb[rows], L[j, rows] = Wl, Wbl, Lj
+        for k, e in enumerate(live):
+            s_enc[e] = s1_enc[k]
+        live = [e for e in live if e not in ended]
+        if not live:
+            break
+    with torch.no_grad():
+        for e in range(E):
+            ws[e].weight.copy_(W[e].view_as(ws[e].weight))
+            ws[e].bias.copy_(Wb[e].view_as(ws[e].bias))
+    Lh = L.cpu().tolist()  # one device read for the group's losses
+    acc = []
+    for e in range(E):
+        a = 0  # accum_loss of test_agent (:240-248): a python sum of .item()
+        for j in range(steps[e]):
+            a += Lh[j][e]
+        acc.append(a)
+    return R, acc
+
+
 def enable(agent, episodes_end=None) -> None:
     """Bind lockstep test rollouts into an SFDQN or TSFDQN instance without touching its code: ``train``
     records its ``test_tasks``; the first ``test_agent`` call of a test phase (test_index 0) runs
@@ -367,8 +483,13 @@ def enable(agent, episodes_end=None) -> None:
     early run the agent's own sequential ``test_agent``."""
     train, state = agent.train, {"tasks": None, "R": None}
     own = agent.test_agent  # the user's sequential loop: the fallback
-    # the TSF agents (test_tasks_weights of (w_approx, optim, scheduler) and per-task ω) or SFDQN
-    rollout = test_tasks_lockstep_tsf if hasattr(agent, "omegas") else test_tasks_lockstep
+
+    def rollout(*args, **kwargs):
+        # chosen per call: the TSF agents (test_tasks_weights of (w_approx, optim, scheduler) and per-task ω),
+        # SFDQN_PHI over sfx's DeepSF_PHI (a learned φ, biased reward models), or SFDQN
+        if hasattr(agent, "omegas"):
+            return test_tasks_lockstep_tsf(*args, **kwargs)
+        return (test_tasks_lockstep_phi if phi_agent(agent) else test_tasks_lockstep)(*args, **kwargs)
 
     def train_recording(*args, **kwargs):
         tasks = kwargs.get("test_tasks", args[4] if len(args) > 4 else [])

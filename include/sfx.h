@@ -605,6 +605,28 @@ int sfx_tsf_phi_test_update(sfx_t h, const float* s_dev, const int64_t* a_dev, f
 int sfx_phi_test_update(sfx_t h, const float* s_dev, const int64_t* a_dev, float r, const float* s1_dev, float* w_dev,
                         float* wb_dev, float* loss_dev);
 
+/* SF-φ's test tasks in lockstep (agents/sfdqn_phi.py:211-212, the loop over test_agent :234-261, with the E
+ * episodes stepped together; sfx/lockstep.py test_tasks_lockstep_phi).  Row e is test task e: S_dev / S1_dev
+ * [E][n_s], a_dev [E], W_dev rows at w_stride (>= d) with the biases in Wb_dev [E], 1 <= E <= min(16, max_batch).
+ * Every row's result is bit for bit what the one-row call gives for it, so a lockstep phase follows the
+ * sequential loop's trajectory exactly.  The preconditions of sfx_phi_test_update; a violation, a null argument,
+ * E out of range or w_stride < d: SFX_E_ARG with the limit in the message.  Nothing of the training state is
+ * written; no per-step scalar arguments (r comes from the device).
+ * sfx_phi_test_actions: SFDQN_PHI.get_test_action's greedy branch (agents/sfdqn_phi.py:223-232 over
+ *   features/deep_phi.py GPI_w) for every row: q[e,t,a] = fl(ψ_t(S[e])[a,:]·W[e,:] + Wb[e]) -- the bias added
+ *   after the dot product, as GPI_w adds it --, c_e = argmax_t max_a q[e,t,a], a_e = argmax_a q[e,c_e,a] (first
+ *   index on ties).  out_dev [E][2] = (c_e, a_e), q_dev [E][T][A] may be NULL.
+ * sfx_phi_test_updates: sfx_phi_test_update (agents/sfdqn_phi.py:263-305) of every row, r_dev [E], loss_dev [E];
+ *   W_dev / Wb_dev updated in place.
+ * sfx_phi_features_rows: phi_dev [E][d], row e = sfx_phi_features(S[e], a[e], S1[e]) at B = 1, the weights
+ *   streamed once per 8 rows (the chain sfx_phi_test_updates runs; for tests and measurements). */
+int sfx_phi_test_actions(sfx_t h, const float* S_dev, int E, const float* W_dev, int w_stride, const float* Wb_dev,
+                         float* q_dev, int64_t* out_dev);
+int sfx_phi_test_updates(sfx_t h, int E, const float* S_dev, const int64_t* a_dev, const float* r_dev,
+                         const float* S1_dev, float* W_dev, int w_stride, float* Wb_dev, float* loss_dev);
+int sfx_phi_features_rows(sfx_t h, const float* S_dev, const int64_t* a_dev, const float* S1_dev, int E,
+                          float* phi_dev);
+
 int sfx_tsf_test_action(sfx_t h, const float* s_dev, const float* w_dev, const float* omega_dev, int64_t* a_dev);
 int sfx_tsf_test_update(sfx_t h, const float* s_dev, const float* s1_dev, const int64_t* a_dev, const int64_t* a1_dev,
                         float r, const float* phi_dev, float* w_dev, float* omega_dev, float* adam_state_dev,
