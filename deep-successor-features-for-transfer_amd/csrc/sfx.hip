@@ -1097,17 +1097,20 @@ struct TsfTail {
   int nblk;
   double bytes;
 };
+// qb: the learned-φ agents' reward-model bias (a device scalar added to every q before the choice, k_sel1m),
+// or null
 int select_pick(sfx_handle* h, int task, int use_gpi, float* q, int64_t* out, const SelPub* pub,
-                const TsfTail* tail = nullptr);
+                const TsfTail* tail = nullptr, const float* qb = nullptr);
 int select_body(sfx_handle* h, const float* s, int task, int use_gpi, float* q, int64_t* out,
-                const SelPub* pub = nullptr) {
+                const SelPub* pub = nullptr, const float* qb = nullptr) {
   RC(run_fwd(h, {{R_A, P_ONLINE, 1, 0, h->T}}, 1, s, nullptr));
-  return select_pick(h, task, use_gpi, q, out, pub);
+  return select_pick(h, task, use_gpi, q, out, pub, nullptr, qb);
 }
 
 // the choice from role R_A row 0 (GPI with w of `task`, or `task`'s own q) and the publication
 int select_pick(sfx_handle* h, int task, int use_gpi, float* q, int64_t* out, const SelPub* pub,
-                const TsfTail* tail) {
+                const TsfTail* tail, const float* qb) {
+  if (qb && (tail || h->T > 64 || h->A > 256)) SFX_FAIL(SFX_E_STATE, "biased selection: only the one-state k_sel1m takes a bias");
   const GpiArgs g = gpi_args(R_A, 0, 0, h->w + (size_t)task * h->dpad, nullptr, q, nullptr, nullptr, out, task, use_gpi, 1);
   const int TA = h->T * h->A;
   if (h->T <= 64 && h->A <= 256) {  // one workgroup per head, the last one picks
@@ -1133,11 +1136,11 @@ int select_pick(sfx_handle* h, int task, int use_gpi, float* q, int64_t* out, co
       return SFX_OK;
     }
     if (h->d % 4 == 0)
-      launch(h, K_GPI, by, k_sel1m<4>, grid, block, h->G, g, P, h->selk);
+      launch(h, K_GPI, by, k_sel1m<4>, grid, block, h->G, g, P, h->selk, qb);
     else if (h->d % 2 == 0)
-      launch(h, K_GPI, by, k_sel1m<2>, grid, block, h->G, g, P, h->selk);
+      launch(h, K_GPI, by, k_sel1m<2>, grid, block, h->G, g, P, h->selk, qb);
     else
-      launch(h, K_GPI, by, k_sel1m<1>, grid, block, h->G, g, P, h->selk);
+      launch(h, K_GPI, by, k_sel1m<1>, grid, block, h->G, g, P, h->selk, qb);
     LAUNCHCHK();
     return SFX_OK;
   }
@@ -1173,6 +1176,13 @@ int update_body(sfx_handle* h, int policy, const float* S, const int64_t* a, con
   td.next_stride = B;
   return run_bwd(h, policy, 1, B, S, phi, r, losses, td);
 }
+
+// DeepSF_PHI.update_successor / TSFDQN_PHI.update_deep_models (sfx_phi.inc)
+int phi_update_body(sfx_handle* h, int transform, int policy, const float* S, const int64_t* a, const float* r,
+                    const float* S1, const float* gamma, int B, int use_gpi, float* bias, float* lambda, float* losses,
+                    int64_t* next);
+int phi_runner_prepare(sfx_handle* h, bool tsf);
+bool phi_runner_ready(const sfx_handle* h, bool tsf);
 
 // TSFDQN.update_successor (sfx_tsf.inc)
 int tsf_body(sfx_handle* h, int policy, const float* S, const int64_t* a, const float* r, const float* phi,

@@ -2770,6 +2770,9 @@ __global__ void k_publish(const int64_t* sel, const int* flag, HostResult* out, 
 // heads (argmax_key(max_a q_t, t)); the action as the first-index argmax over a of q[c][a].  The
 // runner's publication (k_publish) is folded into the last workgroup.  Launch: grid T, 64·⌈A/64⌉
 // threads; selections only (no task_out / next_out).
+// qb (optional, a device scalar): the reward model's bias of the learned-φ agents, q = fl(ψ·w) + b as
+// DeepSF_PHI.GPI_w forms it (features/deep_phi.py) -- added after the dot product and before the keys, since
+// the add can round a near tie into an exact one and move the first argmax index.  Null: no add at all.
 // -------------------------------------------------------------------------------------
 struct SelPub {
   HostResult* res;  // null: no publication
@@ -2788,7 +2791,8 @@ struct SelScratch {
 
 // head t's workgroup of k_sel1m
 template <int VW>  // d % VW == 0
-__device__ __forceinline__ void sel1m_body(const Geo& G, const GpiArgs& A, const SelPub& P, SelScratch* S, int t) {
+__device__ __forceinline__ void sel1m_body(const Geo& G, const GpiArgs& A, const SelPub& P, SelScratch* S, int t,
+                                           const float* qb = nullptr) {
   PROBE_T(pt0);
   __shared__ float s_w[DMAX];
   __shared__ float s_q[256];
@@ -2820,6 +2824,7 @@ __device__ __forceinline__ void sel1m_body(const Geo& G, const GpiArgs& A, const
       }
     }
   }
+  if (qb) q = __fadd_rn(q, *qb);
   if (act) {
     s_q[tid] = q;
     if (A.q_out) A.q_out[(ob * T + t) * Aa + tid] = q;
@@ -2861,8 +2866,8 @@ __device__ __forceinline__ void sel1m_body(const Geo& G, const GpiArgs& A, const
 }
 
 template <int VW>
-__global__ __launch_bounds__(256) void k_sel1m(Geo G, GpiArgs A, SelPub P, SelScratch* S) {
-  sel1m_body<VW>(G, A, P, S, blockIdx.x);
+__global__ __launch_bounds__(256) void k_sel1m(Geo G, GpiArgs A, SelPub P, SelScratch* S, const float* qb) {
+  sel1m_body<VW>(G, A, P, S, blockIdx.x, qb);
 }
 
 }  // namespace sfx

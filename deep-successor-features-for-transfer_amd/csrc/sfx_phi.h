@@ -11,6 +11,10 @@
 //               scaled) + (2/B)(w·φ_b + b - r_b) w; backward through the φ net, then one fresh
 //               Adam step on every φ parameter, on w_i and its bias, and λ_i ← clamp(λ_i + step
 //               of ascent on psi_loss, 1e-2, 1e6); losses (loss, psi_loss, phi_loss, λ_i).
+// Every kernel that steps persistent state (the φ net, w_i, its bias, λ_i) reads PhiArgs::cancel first
+// (step_cancelled, sfx_kernels.h): a runner step cancelled at its gate runs its launches but commits
+// nothing -- these parameters are stepped in place, so a commit would be applied again by the re-issue.
+// Activations, φ, the gradients' buffers and the losses are transient and written either way.
 // A fresh Adam (the reference builds torch.optim.Adam inside every update) has zero moments and
 // step 1: p -= lr / (1 - β1) · m / (√v / √(1 - β2) + ε) with m = (1 - β1) g, v = (1 - β2) g².
 // One workgroup each: the net is tiny (n_in <= 64, hid <= 128, d <= 64) and B <= 64.
@@ -36,6 +40,7 @@ struct PhiArgs {
   float* lam;          // λ_i
   float* losses;       // [4]: loss, psi_loss (losses[1] written by the ψ tail), phi_loss, λ_i after
   AdamHP hp;           // lr of every parameter group (1e-3 in features/deep_phi.py), β, ε
+  const int* cancel;   // runner steps: 1 when the step's gate cancelled it (no commit); 0 otherwise
 };
 
 __device__ __forceinline__ int phi_layer_in(const PhiArgs& A, int l) { return l == 0 ? A.n_in : A.hid; }
@@ -92,11 +97,23 @@ __global__ __launch_bounds__(256) void k_phi_fwd(PhiArgs A) {
   }
 }
 
+// A freshly built Adam for one ψ head: zero moments (the head's read slot) and step 0, which the backward
+// launch bumps to 1.  Not guarded by the cancel word: every learned-φ update begins with this reset, so a
+// cancelled step leaves what the next update writes first anyway.
+__global__ __launch_bounds__(256) void k_phi_fresh(float* m, float* v, int n, int* step) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) {
+    m[i] = 0.f;
+    v[i] = 0.f;
+  }
+  if (i == 0) *step = 0;
+}
+
 // backward through the net from the output gradient g [B][d] (LDS; gn the second buffer), layer
 // L-1 .. 0: dW, db (Σ over rows) with the fresh-Adam step (CL: gradients clamped to [-1, 1] first,
 // agents/tsfdqn_phi.py:268-270), then dX through the ReLU
 template <bool CL>
-__device__ __forceinline__ void phi_bwd_net(const PhiArgs& A, float* g, float* gn, const AdamC& c1) {
+__device__ __forceinline__ void phi_bwd_net(const PhiArgs& A, float* g, float* gn, const AdamC& c1, int cx) {
   const int tid = threadIdx.x, B = A.B, L = A.n_mid + 2;
   for (int l = L - 1; l >= 0; --l) {
     const int K = phi_layer_in(A, l), N = phi_layer_out(A, l);
@@ -118,12 +135,12 @@ __device__ __forceinline__ void phi_bwd_net(const PhiArgs& A, float* g, float* g
       const int o = j / K, k = j - o * K;
       float acc = 0.f;
       for (int b = 0; b < B; ++b) acc = __builtin_fmaf(g[b * N + o], X[(long long)b * xs + k], acc);
-      W[j] = fresh_adam(W[j], CL ? fminf(fmaxf(acc, -1.f), 1.f) : acc, c1);
+      if (!cx) W[j] = fresh_adam(W[j], CL ? fminf(fmaxf(acc, -1.f), 1.f) : acc, c1);
     }
     for (int o = tid; o < N; o += 256) {
       float acc = 0.f;
       for (int b = 0; b < B; ++b) acc = __fadd_rn(acc, g[b * N + o]);
-      bias[o] = fresh_adam(bias[o], CL ? fminf(fmaxf(acc, -1.f), 1.f) : acc, c1);
+      if (!cx) bias[o] = fresh_adam(bias[o], CL ? fminf(fmaxf(acc, -1.f), 1.f) : acc, c1);
     }
     __syncthreads();
     float* t = g;
@@ -137,6 +154,7 @@ __global__ __launch_bounds__(256) void k_phi_bwd(PhiArgs A) {
   __shared__ float s_w[PHI_IN], s_e[PHI_B];
   const int tid = threadIdx.x, B = A.B, d = A.d;
   const AdamC c1 = adam_consts(A.hp, 1);
+  const int cx = step_cancelled(A.cancel);
   if (tid < d) s_w[tid] = A.w[tid];
   __syncthreads();
   const float wb = *A.wb;
@@ -160,7 +178,7 @@ __global__ __launch_bounds__(256) void k_phi_bwd(PhiArgs A) {
   if (tid < d) {
     float g = 0.f;
     for (int b = 0; b < B; ++b) g = __builtin_fmaf(__fmul_rn(nrm, s_e[b]), A.phis[(long long)b * d + tid], g);
-    A.w[tid] = fresh_adam(s_w[tid], g, c1);
+    if (!cx) A.w[tid] = fresh_adam(s_w[tid], g, c1);
   }
   if (tid == 0) {
     float gb = 0.f, sse = 0.f;
@@ -168,17 +186,17 @@ __global__ __launch_bounds__(256) void k_phi_bwd(PhiArgs A) {
       gb = __fadd_rn(gb, __fmul_rn(nrm, s_e[b]));
       sse = __builtin_fmaf(s_e[b], s_e[b], sse);
     }
-    *A.wb = fresh_adam(wb, gb, c1);
+    if (!cx) *A.wb = fresh_adam(wb, gb, c1);
     const float phi_loss = (float)((double)sse / (double)B);
     const float psi_loss = A.losses[1];
     const float lam = *A.lam;
     A.losses[0] = __fadd_rn(phi_loss, __fmul_rn(lam, psi_loss));
     A.losses[2] = phi_loss;
     const float ln = fminf(fmaxf(fresh_adam(lam, psi_loss, c1, true), 1e-2f), 1e6f);
-    *A.lam = ln;
+    if (!cx) *A.lam = ln;
     A.losses[3] = ln;
   }
-  phi_bwd_net<false>(A, sg, sg2, c1);
+  phi_bwd_net<false>(A, sg, sg2, c1, cx);
 }
 
 // the φ net's backward from an output gradient in memory (gtop [B][d], sfx_tsfphi.h k_tsfphi_bwd)
@@ -187,7 +205,7 @@ __global__ __launch_bounds__(256) void k_phi_bwd_top(PhiArgs A, const float* gto
   const AdamC c1 = adam_consts(A.hp, 1);
   for (int j = threadIdx.x; j < A.B * A.d; j += 256) sg[j] = gtop[j];
   __syncthreads();
-  phi_bwd_net<true>(A, sg, sg2, c1);
+  phi_bwd_net<true>(A, sg, sg2, c1, step_cancelled(A.cancel));
 }
 
 }  // namespace sfx

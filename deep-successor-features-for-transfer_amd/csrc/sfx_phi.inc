@@ -40,6 +40,7 @@ PhiArgs phi_args(sfx_handle* h, int pol, int B) {
   A.w = h->w + (size_t)pol * h->dpad;
   A.dzlast = h->dz + (size_t)pol * h->actSize + A.lastOff;
   A.hp = AdamHP{s->lr, 0.0, h->hp_psi.b1, h->hp_psi.b2, h->hp_psi.eps};
+  A.cancel = h->dcancel;
   return A;
 }
 
@@ -157,6 +158,7 @@ PhiwLayer phiw_layer(sfx_handle* h, int l, int B, int clamp) {
   A.relu = l < L - 1;
   A.clamp = clamp;
   A.hp = AdamHP{s->lr, 0.0, h->hp_psi.b1, h->hp_psi.b2, h->hp_psi.eps};
+  A.cancel = h->dcancel;
   return A;
 }
 
@@ -212,7 +214,131 @@ int phiw_backward(sfx_handle* h, int B, int clamp) {
   return SFX_OK;
 }
 
-// DeepSF_PHI.update_successor (transform = 0) / TSFDQN_PHI.update_deep_models (transform = 1)
+// DeepSF_PHI.update_successor (transform = 0) / TSFDQN_PHI.update_deep_models (transform = 1) of one head:
+// launches only (update_body's shape), shared by sfx_phi_update, sfx_tsf_phi_update and the runner's learned-φ
+// steps, so all three produce the same bits.  The buffers of phi_lazy_buffers must exist already (it allocates:
+// never inside a capture).  Under a runner gate every commit honours the step's cancel word: the ψ launches
+// through Geo::cancel, the φ kernels through PhiArgs / TsfPhiArgs / PhiwLayer::cancel.
+int phi_update_body(sfx_handle* h, int transform, int policy, const float* S, const int64_t* a, const float* r,
+                    const float* S1, const float* gamma, int B, int use_gpi, float* bias, float* lambda, float* losses,
+                    int64_t* next) {
+  sfx_phi_state* s = h->phi;
+  PhiArgs A = phi_args(h, policy, B);
+  A.S = S;
+  A.S1 = S1;
+  A.a = a;
+  A.r = r;
+  A.wb = bias;
+  A.lam = lambda;
+  A.losses = losses;
+  TsfPhiArgs Q{};
+  Q.B = B;
+  Q.d = h->d;
+  Q.n_s = h->n_s;
+  Q.O = h->O;
+  Q.transform = transform;
+  Q.clamp = transform;
+  Q.S = S;
+  Q.S1 = S1;
+  Q.a = a;
+  Q.r = r;
+  if (transform) {
+    Q.g = h->tsf->g + (size_t)policy * h->tsf->Pg;
+    Q.hp = h->tsf->hp;
+  }
+  Q.phis = s->phis;
+  Q.tphi = transform ? s->tphi : s->phis;
+  Q.tt = s->tt;
+  Q.usum = s->usum;
+  Q.dzlast = A.dzlast;
+  Q.gtop = s->gbuf;
+  Q.w = A.w;
+  Q.wb = bias;
+  Q.lam = lambda;
+  Q.losses = losses;
+  Q.hpa = A.hp;
+  Q.cancel = h->dcancel;
+  const double P = s->P, Bd = B, bd = Bd * h->d;
+  if (s->wide) {
+    RC(phiw_forward(h, B, S, a, S1));
+  } else {
+    launch(h, K_TSF, 4.0 * (P + Bd * (s->n_in + (s->n_mid + 1.0) * s->hid + h->d)), k_phi_fwd, dim3(1), dim3(256), A);
+    LAUNCHCHK();
+  }
+  if (transform) {
+    launch(h, K_TSF, 4.0 * (2.0 * Bd * h->n_s + 4.0 * bd + h->tsf->Pg + h->tsf->Ph), k_tsfphi_fwd, dim3(1), dim3(256),
+           Q);
+    LAUNCHCHK();
+  }
+  // the ψ update with φ (φ̃) as the features: λ-scaled output gradient, fresh Adam, psi_loss into losses[1]
+  if (use_gpi)
+    RC(run_fwd(h, {{R_S, P_ONLINE, 1, policy, 1}, {R_S1T, P_TARGET, 2, policy, 1}, {R_S1, P_ONLINE, 2, 0, h->T}}, B,
+               S, S1));
+  else
+    RC(run_fwd(h, {{R_S, P_ONLINE, 1, policy, 1}, {R_S1T, P_TARGET, 2, policy, 1}, {R_S1, P_ONLINE, 2, policy, 1}},
+               B, S, S1));
+  // a freshly built Adam (features/deep_phi.py:163-175, agents/tsfdqn_phi.py:249 make one per update):
+  // zero moments in the head's read slot and step 0, which the backward bumps to 1 (its bias corrections).
+  // No cancel guard on this reset: every learned-φ update starts from zero moments and step 0, so a
+  // cancelled runner step that zeroed them leaves exactly what its re-issue (and any later φ update of
+  // the head) would write first anyway.  It is a kernel (k_phi_fresh), not three hipMemsetAsync: as memset
+  // nodes of the runner's step graphs -- launched behind a step that is still running, their gates giving
+  // up -- the resets did not stay in order with the kernels around them (measured: non-finite heads after
+  // the first cancelled step with memset nodes, bit-exact runs with the kernel), and every other schedule's
+  // step graph is kernel nodes only.
+  const size_t ro = ((size_t)h->slot(policy) * h->T + policy) * h->P;
+  touch(h);
+  launch(h, K_TSF, 8.0 * h->P, k_phi_fresh, dim3(cdiv(h->P, 256)), dim3(256), h->am + ro, h->av + ro, h->P,
+         h->step + policy);
+  LAUNCHCHK();
+  TdgSpec td;
+  td.use_gpi = use_gpi;
+  td.a = a;
+  td.gamma = gamma;
+  td.next = next;
+  td.next_stride = B;
+  td.dz_scale = lambda;
+  RC(run_bwd(h, policy, 1, B, S, Q.tphi, nullptr, losses, td));
+  if (!s->wide && !transform) {
+    launch(h, K_TSF, 4.0 * (3.0 * P + Bd * ((s->n_mid + 1.0) * s->hid + s->n_in + 2.0 * h->d + h->O)), k_phi_bwd,
+           dim3(1), dim3(256), A);
+    LAUNCHCHK();
+    return SFX_OK;
+  }
+  launch(h, K_TSF, 4.0 * (Bd * h->O + 6.0 * bd + (transform ? 2.0 * (h->tsf->Pg + h->tsf->Ph) : 0.0)), k_tsfphi_bwd,
+         dim3(1), dim3(256), Q);
+  LAUNCHCHK();
+  if (s->wide) {
+    RC(phiw_backward(h, B, transform));
+  } else {
+    launch(h, K_TSF, 4.0 * (3.0 * P + Bd * ((s->n_mid + 1.0) * s->hid + s->n_in + h->d)), k_phi_bwd_top, dim3(1),
+           dim3(256), A, (const float*)s->gbuf);
+    LAUNCHCHK();
+  }
+  return SFX_OK;
+}
+
+// What the runner's learned-φ schedules need of the handle (sfx_runner_config): SFX_E_STATE naming the missing
+// piece, else the update's lazily allocated buffers are made now, outside any capture.
+int phi_runner_prepare(sfx_handle* h, bool tsf) {
+  if (h->Tg != h->T) SFX_FAIL(SFX_E_STATE, "sfx_runner_config: the learned-φ schedules need an unsharded handle");
+  if (!h->phi)
+    SFX_FAIL(SFX_E_STATE, "sfx_runner_config: the learned-φ schedules need a φ net (sfx_phi_setup or sfx_phi_setup_dims)");
+  if (tsf && (!h->tsf || h->tsf->G != h->d || h->tsf->K != 0))
+    SFX_FAIL(SFX_E_STATE, "sfx_runner_config: the tsf_phi schedule needs sfx_tsf_setup(G = d, K = 0) (g_i, h plain Linear)");
+  if (h->T > 64 || h->A > 256)
+    SFX_FAIL(SFX_E_STATE, "sfx_runner_config: the biased selection of the learned-φ schedules needs T <= 64 and A <= 256");
+  if (tsf || h->phi->wide) RC(phi_lazy_buffers(h, tsf));
+  return SFX_OK;
+}
+
+// still so at a step's capture?  (a φ or TSF setup made after sfx_runner_config replaces the state and its buffers)
+bool phi_runner_ready(const sfx_handle* h, bool tsf) {
+  const sfx_phi_state* s = h->phi;
+  if (!s || h->Tg != h->T || ((tsf || s->wide) && !s->gbuf)) return false;
+  return !tsf || (s->tphi && s->tt && s->usum && h->tsf && h->tsf->G == h->d && h->tsf->K == 0);
+}
+
 int phi_update_impl(sfx_handle* h, int op, int transform, int policy, const float* S, const int64_t* a, const float* r,
                     const float* S1, const float* gamma, int B, int use_gpi, float* bias, float* lambda, float* losses,
                     int64_t* next) {
@@ -220,92 +346,7 @@ int phi_update_impl(sfx_handle* h, int op, int transform, int policy, const floa
   const GraphKey key =
       make_key(op, {policy, B, use_gpi ? 1 : 0}, h->mask, {S, a, r, S1, gamma, bias, lambda, losses, next});
   RC(run_graph(h, key, [&]() -> int {
-    sfx_phi_state* s = h->phi;
-    PhiArgs A = phi_args(h, policy, B);
-    A.S = S;
-    A.S1 = S1;
-    A.a = a;
-    A.r = r;
-    A.wb = bias;
-    A.lam = lambda;
-    A.losses = losses;
-    TsfPhiArgs Q{};
-    Q.B = B;
-    Q.d = h->d;
-    Q.n_s = h->n_s;
-    Q.O = h->O;
-    Q.transform = transform;
-    Q.clamp = transform;
-    Q.S = S;
-    Q.S1 = S1;
-    Q.a = a;
-    Q.r = r;
-    if (transform) {
-      Q.g = h->tsf->g + (size_t)policy * h->tsf->Pg;
-      Q.hp = h->tsf->hp;
-    }
-    Q.phis = s->phis;
-    Q.tphi = transform ? s->tphi : s->phis;
-    Q.tt = s->tt;
-    Q.usum = s->usum;
-    Q.dzlast = A.dzlast;
-    Q.gtop = s->gbuf;
-    Q.w = A.w;
-    Q.wb = bias;
-    Q.lam = lambda;
-    Q.losses = losses;
-    Q.hpa = A.hp;
-    const double P = s->P, Bd = B, bd = Bd * h->d;
-    if (s->wide) {
-      RC(phiw_forward(h, B, S, a, S1));
-    } else {
-      launch(h, K_TSF, 4.0 * (P + Bd * (s->n_in + (s->n_mid + 1.0) * s->hid + h->d)), k_phi_fwd, dim3(1), dim3(256), A);
-      LAUNCHCHK();
-    }
-    if (transform) {
-      launch(h, K_TSF, 4.0 * (2.0 * Bd * h->n_s + 4.0 * bd + h->tsf->Pg + h->tsf->Ph), k_tsfphi_fwd, dim3(1), dim3(256),
-             Q);
-      LAUNCHCHK();
-    }
-    // the ψ update with φ (φ̃) as the features: λ-scaled output gradient, fresh Adam, psi_loss into losses[1]
-    if (use_gpi)
-      RC(run_fwd(h, {{R_S, P_ONLINE, 1, policy, 1}, {R_S1T, P_TARGET, 2, policy, 1}, {R_S1, P_ONLINE, 2, 0, h->T}}, B,
-                 S, S1));
-    else
-      RC(run_fwd(h, {{R_S, P_ONLINE, 1, policy, 1}, {R_S1T, P_TARGET, 2, policy, 1}, {R_S1, P_ONLINE, 2, policy, 1}},
-                 B, S, S1));
-    // a freshly built Adam (features/deep_phi.py:163-175, agents/tsfdqn_phi.py:249 make one per update):
-    // zero moments in the head's read slot and step 0, which the backward bumps to 1 (its bias corrections)
-    const size_t ro = ((size_t)h->slot(policy) * h->T + policy) * h->P;
-    touch(h);
-    HIPCHK(hipMemsetAsync(h->am + ro, 0, sizeof(float) * h->P, h->stream));
-    HIPCHK(hipMemsetAsync(h->av + ro, 0, sizeof(float) * h->P, h->stream));
-    HIPCHK(hipMemsetAsync(h->step + policy, 0, sizeof(int), h->stream));
-    TdgSpec td;
-    td.use_gpi = use_gpi;
-    td.a = a;
-    td.gamma = gamma;
-    td.next = next;
-    td.next_stride = B;
-    td.dz_scale = lambda;
-    RC(run_bwd(h, policy, 1, B, S, Q.tphi, nullptr, losses, td));
-    if (!s->wide && !transform) {
-      launch(h, K_TSF, 4.0 * (3.0 * P + Bd * ((s->n_mid + 1.0) * s->hid + s->n_in + 2.0 * h->d + h->O)), k_phi_bwd,
-             dim3(1), dim3(256), A);
-      LAUNCHCHK();
-      return SFX_OK;
-    }
-    launch(h, K_TSF, 4.0 * (Bd * h->O + 6.0 * bd + (transform ? 2.0 * (h->tsf->Pg + h->tsf->Ph) : 0.0)), k_tsfphi_bwd,
-           dim3(1), dim3(256), Q);
-    LAUNCHCHK();
-    if (s->wide) {
-      RC(phiw_backward(h, B, transform));
-    } else {
-      launch(h, K_TSF, 4.0 * (3.0 * P + Bd * ((s->n_mid + 1.0) * s->hid + s->n_in + h->d)), k_phi_bwd_top, dim3(1),
-             dim3(256), A, (const float*)s->gbuf);
-      LAUNCHCHK();
-    }
-    return SFX_OK;
+    return phi_update_body(h, transform, policy, S, a, r, S1, gamma, B, use_gpi, bias, lambda, losses, next);
   }));
   h->mask ^= 1ull << policy;
   after_update(h, policy);

@@ -25,6 +25,8 @@
 // No floating-point atomics and a fixed reduction order everywhere: two runs from the same state
 // give the same bits.  Bytes per update at hid 2048, n_mid 3: forward P·4, dX (P - first layer)·4,
 // dW 2·P·4 -- four passes over ≈50 MB.
+// k_phiw_dw is the one kernel here that writes persistent state (W and the bias, in place): a runner step
+// cancelled at its gate (PhiwLayer::cancel, step_cancelled in sfx_kernels.h) leaves before it loads anything.
 #pragma once
 
 namespace sfx {
@@ -39,6 +41,7 @@ struct PhiwLayer {
   float* GX;       // dX: [B][K] gradient at the pre-activation output of the layer below
   int K, N, B, relu, clamp;
   AdamHP hp;
+  const int* cancel;  // runner steps: 1 when the step's gate cancelled it (k_phiw_dw commits nothing)
 };
 
 __device__ __forceinline__ bool phiw_vec(const void* p, int stride, int n) {
@@ -204,6 +207,7 @@ __global__ __launch_bounds__(256) void k_phiw_dw(PhiwLayer A) {
   const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, g = l >> 4, c = l & 15;
   const int K = A.K, N = A.N, B = A.B;
   const int o0 = blockIdx.x * 16, k0 = (blockIdx.y * 4 + w) * 64;
+  if (step_cancelled(A.cancel)) return;  // uniform: the tile's only output is the stepped W / bias
   const AdamC c1 = adam_consts(A.hp, 1);
   const float* __restrict__ G = A.G;
   const float* __restrict__ X = A.X;

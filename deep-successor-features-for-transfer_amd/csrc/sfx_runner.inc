@@ -9,6 +9,13 @@
 //   active sfdqn.py:462-471 / agents/sfdqn_sequential.py:63-76: only the active task's head is
 //          updated (l1 + l2, Adam-trained w), no LMS;
 //   tsf    tsfdqn.py:566-580 / tsfdqn_nf.py:598-612: TSFDQN.update_successor of the active task.
+//   phi    agents/sfdqn_phi.py:80-109 over features/deep_phi.py: GPI with the active task's biased reward
+//          model (q = ψ·w + b), ε-greedy, env transition, append (the env's φ is not used), replay,
+//          DeepSF_PHI.update_successor of the active head (phi_update_body, sfx_phi.inc);
+//   tsf_phi agents/tsfdqn_phi.py:80-103 over features/deep_tsf_phi.py: the same loop with
+//          TSFDQN_PHI.update_deep_models (φ̃ = φ ⊙ t, g_i and h plain Linears).
+//          Both step the φ net, w_i, its bias, λ_i (and g_i, h) in place, so every one of their kernels
+//          honours the gate's cancel word; no look-ahead and no device replay yet.
 // The env and the replay ring stay on the host (north_star); the device work of a step is one
 // hipGraph: k_gate -> the step's update -> the action for the next state -> publish.
 //
@@ -25,7 +32,8 @@ namespace {
 
 // Staging record of one step: the minibatch [s .. rb], then the tail the host writes every
 // step [snext .. tr_meta] (with device replay only the tail crosses PCIe).
-enum { RUN_ALL = 0, RUN_ACTIVE = 1, RUN_TSF = 2, RUN_SHARD = 3, RUN_SHARD_TSF = 4 };
+enum { RUN_ALL = 0, RUN_ACTIVE = 1, RUN_TSF = 2, RUN_SHARD = 3, RUN_SHARD_TSF = 4, RUN_PHI = 5, RUN_TSF_PHI = 6 };
+constexpr int RUN_SCHEDULES = 8;  // graph-key factor: room for every schedule above
 
 struct RunnerLayout {
   size_t s, s1, phi, a, gamma, snext, phi1, r1, rb, bytes;
@@ -73,7 +81,9 @@ struct sfx_runner {
   int B = 32, cap = 0, ep_len = 500, sel_use_gpi = 1, pipeline = 1;
   int schedule = RUN_ALL, upd_use_gpi = 1;  // sfx_runner_config
   float gamma = 0.9f, eps = 0.1f, alpha_w = 1e-3f, p_end = 0.f;
-  float* dloss = nullptr;  // device [3]: losses of the active-task update (not read back)
+  float* dloss = nullptr;  // device [DLOSS_N]: losses of the active-task update (read back by sfx_runner_phi_losses only)
+  static constexpr int DLOSS_N = 16;
+  float *phi_bias = nullptr, *phi_lam = nullptr;  // sfx_runner_phi_scalars: caller-owned device [T] each
   std::mt19937_64 rng;
   sfx_env_reset_fn env_reset = nullptr;
   sfx_env_step_fn env_step = nullptr;
@@ -173,6 +183,7 @@ int shard_tsf_body(sfx_runner* R, bool have, bool pre, bool ahead);  // sfx_tsf.
 int shard_tsf_buffers(sfx_handle* h);
 
 bool sharded_sched(const sfx_runner* R) { return R->schedule == RUN_SHARD || R->schedule == RUN_SHARD_TSF; }
+bool phi_sched(int schedule) { return schedule == RUN_PHI || schedule == RUN_TSF_PHI; }
 // the local head of the active task on this rank (sharded TSF: -1 when another rank owns it)
 int own_loc(const sfx_runner* R) {
   if (R->schedule != RUN_SHARD_TSF) return R->task;
@@ -463,7 +474,14 @@ int runner_body(sfx_runner* R, bool have, bool lms, sfx_runner::StepFlags fl = {
   }
   if (R->schedule != RUN_ALL) {
     const int64_t* a = reinterpret_cast<const int64_t*>(R->dst + R->lay.a);
-    if (have) {  // pre: the previous step's select forwarded this minibatch (select_ahead_body)
+    const bool phis = phi_sched(R->schedule);
+    if (phis && !phi_runner_ready(h, R->schedule == RUN_TSF_PHI))
+      SFX_FAIL(SFX_E_STATE, "runner: the φ / TSF setup changed after sfx_runner_config; configure the schedule again");
+    if (have && phis) {  // the staged φ rows are not read: φ comes from the net
+      RC(phi_update_body(h, R->schedule == RUN_TSF_PHI ? 1 : 0, R->task, at(R->lay.s), a, at(R->lay.rb), at(R->lay.s1),
+                         at(R->lay.gamma), R->B, R->upd_use_gpi, R->phi_bias + R->task, R->phi_lam + R->task, R->dloss,
+                         nullptr));
+    } else if (have) {  // pre: the previous step's select forwarded this minibatch (select_ahead_body)
       if (R->schedule == RUN_TSF)
         RC(tsf_body(h, R->task, at(R->lay.s), a, at(R->lay.rb), at(R->lay.phi), at(R->lay.s1), at(R->lay.gamma), R->B,
                     R->upd_use_gpi, R->dloss, nullptr, nullptr, pre));
@@ -479,7 +497,8 @@ int runner_body(sfx_runner* R, bool have, bool lms, sfx_runner::StepFlags fl = {
     const int rc = ahead ? select_ahead_body(h, at(R->lay.snext), at(R->lay.ax),
                                              R->schedule == RUN_TSF ? at(R->lay.axphi) : nullptr, R->B, R->task,
                                              R->sel_use_gpi, h->dout->sel, &pub)
-                         : select_body(h, at(R->lay.snext), R->task, R->sel_use_gpi, nullptr, h->dout->sel, &pub);
+                         : select_body(h, at(R->lay.snext), R->task, R->sel_use_gpi, nullptr, h->dout->sel, &pub,
+                                       phis ? R->phi_bias + R->task : nullptr);
     h->mask = saved;
     return rc;
   }
@@ -522,9 +541,10 @@ int runner_launch(sfx_runner* R, bool have, bool lms, int nsteps = 1, bool launc
   }
   const GraphKey key =
       make_key(6, {have ? R->B : 0, lms ? R->task : -1, R->task, R->sel_use_gpi, (int)alpha_bits,
-                   h->spec_rounds * 4 + R->schedule,
+                   h->spec_rounds * RUN_SCHEDULES + R->schedule,
                    R->dev_replay + 2 * R->upd_use_gpi + 4 * nsteps + 128 * fl0.pre + 256 * fl0.ahead + 512 * fl0.par},
-               h->mask, {R->dst, R->hst, R->go, R->res});
+               h->mask, {R->dst, R->hst, R->go, R->res, phi_sched(R->schedule) ? R->phi_bias : nullptr,
+                         phi_sched(R->schedule) ? R->phi_lam : nullptr});
   return run_graph(h, key, [&]() -> int {
     const unsigned long long m0 = h->mask;
     int rc = SFX_OK;
@@ -1156,7 +1176,9 @@ int sfx_runner_create(sfx_runner_t* out, sfx_t h, int batch, int capacity, float
     fail("hipHostMalloc(result) failed");
   if (!rc && hipMalloc((void**)&R->dst, R->lay.bytes) != hipSuccess) fail("hipMalloc(staging) failed");
   if (!rc && hipMalloc((void**)&R->dctr, 64) != hipSuccess) fail("hipMalloc(counter) failed");
-  if (!rc && hipMalloc((void**)&R->dloss, 64) != hipSuccess) fail("hipMalloc(losses) failed");
+  if (!rc && (hipMalloc((void**)&R->dloss, sizeof(float) * sfx_runner::DLOSS_N) != hipSuccess ||
+              hipMemset(R->dloss, 0, sizeof(float) * sfx_runner::DLOSS_N) != hipSuccess))
+    fail("hipMalloc(losses) failed");
   if (!rc) {
     if (hipExtMallocWithFlags((void**)&R->dpush, R->lay.bytes, hipDeviceMallocFinegrained) != hipSuccess ||
         hipExtMallocWithFlags((void**)&R->dgo, 64, hipDeviceMallocFinegrained) != hipSuccess ||
@@ -1219,7 +1241,7 @@ int sfx_runner_layout(sfx_runner_t R, int64_t* offsets_host) {
 }
 
 int sfx_runner_config(sfx_runner_t R, int schedule, int use_gpi, float p_end) {
-  if (!R || schedule < RUN_ALL || schedule > RUN_SHARD_TSF || p_end < 0.f || p_end > 1.f) SFX_FAIL(SFX_E_ARG, "bad args");
+  if (!R || schedule < RUN_ALL || schedule > RUN_TSF_PHI || p_end < 0.f || p_end > 1.f) SFX_FAIL(SFX_E_ARG, "bad args");
   if ((schedule == RUN_TSF || schedule == RUN_SHARD_TSF) && !R->h->tsf)
     SFX_FAIL(SFX_E_STATE, "sfx_runner_config: tsf schedule needs sfx_tsf_setup");
   if ((schedule == RUN_SHARD || schedule == RUN_SHARD_TSF) && R->h->comm_world < 1)
@@ -1228,6 +1250,13 @@ int sfx_runner_config(sfx_runner_t R, int schedule, int use_gpi, float p_end) {
     SFX_FAIL(SFX_E_ARG, "sfx_runner_config: the sharded schedule is features/deep.py's all-task update (GPI next actions)");
   RC(runner_complete(R));
   if (R->pre_n) SFX_FAIL(SFX_E_STATE, "sfx_runner_config: a step is pre-launched");
+  if (phi_sched(schedule)) {
+    if (!R->phi_bias || !R->phi_lam)
+      SFX_FAIL(SFX_E_STATE, "sfx_runner_config: the learned-φ schedules need the per-task scalars (sfx_runner_phi_scalars)");
+    if (R->dev_replay)
+      SFX_FAIL(SFX_E_STATE, "sfx_runner_config: the learned-φ schedules do not run with device replay (switch it off first)");
+    RC(phi_runner_prepare(R->h, schedule == RUN_TSF_PHI));  // allocates: here, never inside a capture
+  }
   if (schedule == RUN_SHARD || schedule == RUN_SHARD_TSF) {
     RC(schedule == RUN_SHARD ? shard_buffers(R->h) : shard_tsf_buffers(R->h));
     R->gpi_counters.assign((size_t)R->h->Tg * R->h->Tg, 0);
@@ -1246,6 +1275,8 @@ int sfx_runner_device_replay(sfx_runner_t R, int enable) {
   RunnerScope scope(R->h);
   RC(runner_complete(R));
   if (R->pre_n) SFX_FAIL(SFX_E_STATE, "sfx_runner_device_replay: a step is pre-launched");
+  if (enable && phi_sched(R->schedule))
+    SFX_FAIL(SFX_E_STATE, "sfx_runner_device_replay: the learned-φ schedules (phi, tsf_phi) keep the replay on the host");
   if (enable && !R->drs) {
     if (R->lay.ax - R->lay.snext > (size_t)REPLAY_TAIL_MAX)
       SFX_FAIL(SFX_E_ARG, "sfx_runner_device_replay: state / feature sizes exceed the gate's staging");
@@ -1294,7 +1325,7 @@ int runner_run(sfx_runner* R, int n);
 // forward holds the extra rows, and to the active-task and TSF schedules (their select forwards the
 // next minibatch; TSF: with its kernels on the step stream) (SFX_AHEAD=0: off)
 bool runner_ahead_ok(const sfx_runner* R) {
-  if (!R->ahead_on || R->dev_replay) return false;
+  if (!R->ahead_on || R->dev_replay || phi_sched(R->schedule)) return false;  // learned φ: no look-ahead yet
   if (R->schedule == RUN_ALL) return can_fuse_ahead(R->h, R->B + 1, R->B);
   // the sharded all-task step whose maxima come from k_qmax launches (the fused maxima accumulate
   // round 0's GPI terms in the step's own S1 forward)
@@ -1519,6 +1550,29 @@ int sfx_runner_ahead_stats(sfx_runner_t R, long long* pre_steps, long long* own_
   if (!R) SFX_FAIL(SFX_E_ARG, "null runner");
   if (pre_steps) *pre_steps = R->pre_steps;
   if (own_forward_steps) *own_forward_steps = R->dirty_steps;
+  return SFX_OK;
+}
+
+int sfx_runner_phi_scalars(sfx_runner_t R, float* bias_dev, float* lambda_dev) {
+  if (!R || !bias_dev || !lambda_dev) SFX_FAIL(SFX_E_ARG, "sfx_runner_phi_scalars: null argument");
+  RunnerScope scope(R->h);
+  RC(runner_complete(R));
+  if (R->pre_n) SFX_FAIL(SFX_E_STATE, "sfx_runner_phi_scalars: a step is pre-launched");
+  R->phi_bias = bias_dev;
+  R->phi_lam = lambda_dev;
+  return SFX_OK;
+}
+
+int sfx_runner_phi_losses(sfx_runner_t R, float* out_host) {
+  static_assert(sfx_runner::DLOSS_N >= 4, "the runner's loss buffer holds (loss, psi_loss, phi_loss, lambda)");
+  if (!R || !out_host) SFX_FAIL(SFX_E_ARG, "sfx_runner_phi_losses: null argument");
+  if (!phi_sched(R->schedule)) SFX_FAIL(SFX_E_STATE, "sfx_runner_phi_losses: the schedule is not phi or tsf_phi");
+  RunnerScope scope(R->h);
+  RC(runner_complete(R));
+  // between runs nothing is queued behind the completed step (a queued step's gate would hold the stream)
+  if (R->pre_n) SFX_FAIL(SFX_E_STATE, "sfx_runner_phi_losses: a step is pre-launched");
+  HIPCHK(hipStreamSynchronize(R->h->stream));
+  HIPCHK(hipMemcpy(out_host, R->dloss, sizeof(float) * 4, hipMemcpyDeviceToHost));
   return SFX_OK;
 }
 

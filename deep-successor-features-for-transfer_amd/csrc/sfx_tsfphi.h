@@ -23,6 +23,10 @@
 // alone and does not clamp: a fresh Adam's step is lr·g/(|g| + ε), for |g| >= 1 that is ±lr to within
 // one ulp of the step with or without the clamp (ε = 1e-8 is below half an ulp of |g| >= 1), and for
 // |g| < 1 the clamp is the identity.
+//
+// k_tsfphi_bwd steps w_i, its bias, λ_i, g_i and h in place: it reads TsfPhiArgs::cancel first and a runner
+// step cancelled at its gate commits none of them (step_cancelled, sfx_kernels.h); dφ and the losses are
+// transient and written either way.
 #pragma once
 
 namespace sfx {
@@ -46,6 +50,7 @@ struct TsfPhiArgs {
   float* lam;           // λ_i
   float* losses;        // [4]: loss, psi_loss (written by the ψ tail), phi_loss, λ_i after
   AdamHP hpa;
+  const int* cancel;    // runner steps: 1 when the step's gate cancelled it (no commit); 0 otherwise
 };
 
 __device__ __forceinline__ float tsfphi_clamp(float g, int on) { return on ? fminf(fmaxf(g, -1.f), 1.f) : g; }
@@ -84,6 +89,7 @@ __global__ __launch_bounds__(256) void k_tsfphi_bwd(TsfPhiArgs A) {
   __shared__ float s_w[PHI_IN], s_e[PHI_B];
   const int tid = threadIdx.x, B = A.B, d = A.d, n_s = A.n_s;
   const AdamC c1 = adam_consts(A.hpa, 1);
+  const int cx = step_cancelled(A.cancel);
   if (tid < d) s_w[tid] = A.w[tid];
   __syncthreads();
   const float wb = *A.wb;
@@ -112,7 +118,7 @@ __global__ __launch_bounds__(256) void k_tsfphi_bwd(TsfPhiArgs A) {
   if (tid < d) {
     float g = 0.f;
     for (int b = 0; b < B; ++b) g = __builtin_fmaf(__fmul_rn(nrm, s_e[b]), A.tphi[(long long)b * d + tid], g);
-    A.w[tid] = fresh_adam(s_w[tid], tsfphi_clamp(g, A.clamp), c1);
+    if (!cx) A.w[tid] = fresh_adam(s_w[tid], tsfphi_clamp(g, A.clamp), c1);
   }
   if (tid == 64) {
     float gb = 0.f, sse = 0.f;
@@ -120,17 +126,17 @@ __global__ __launch_bounds__(256) void k_tsfphi_bwd(TsfPhiArgs A) {
       gb = __fadd_rn(gb, __fmul_rn(nrm, s_e[b]));
       sse = __builtin_fmaf(s_e[b], s_e[b], sse);
     }
-    *A.wb = fresh_adam(wb, tsfphi_clamp(gb, A.clamp), c1);
+    if (!cx) *A.wb = fresh_adam(wb, tsfphi_clamp(gb, A.clamp), c1);
     const float phi_loss = (float)((double)sse / (double)B);
     const float psi_loss = A.losses[1];
     const float lam = *A.lam;
     A.losses[0] = __fadd_rn(phi_loss, __fmul_rn(lam, psi_loss));
     A.losses[2] = phi_loss;
     const float ln = fminf(fmaxf(fresh_adam(lam, tsfphi_clamp(psi_loss, A.clamp), c1, true), 1e-2f), 1e6f);
-    *A.lam = ln;
+    if (!cx) *A.lam = ln;
     A.losses[3] = ln;
   }
-  if (!A.transform) return;
+  if (!A.transform || cx) return;  // cancelled: g_i and h keep their values (cx is uniform)
   __syncthreads();
   float* Wg = A.g;
   float* bg = A.g + d * n_s;

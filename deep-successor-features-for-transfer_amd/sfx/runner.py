@@ -229,21 +229,29 @@ class NativeEnvLoop:
     (TSFDQN.update_successor; needs SFEngine.tsf_setup), "sharded" (the all-task step with the
     heads split over ranks, BASELINE config C4) or "sharded_tsf" (the TSF step with the heads split
     over ranks, config C5: tsf_setup + shard_setup + a communicator; the active task is a global
-    index and its owner updates).  p_end: per-step episode-end
+    index and its owner updates), "phi" (agents/sfdqn_phi.py over features/deep_phi.py: the learned-φ SF
+    agent's training step -- biased GPI selection, DeepSF_PHI.update_successor of the active head; needs
+    SFEngine.phi_setup / phi_setup_dims) or "tsf_phi" (agents/tsfdqn_phi.py over features/deep_tsf_phi.py;
+    needs a φ setup and tsf_setup(G = d, K = 0)).  The two learned-φ schedules take phi_bias / phi_lambda:
+    float32 device tensors of T elements, the tasks' reward-model biases and loss coefficients, read and
+    updated in place by the steps (kept alive by the loop); phi_losses() returns what the agents log.  They
+    run with the host replay only and do not look ahead.  p_end: per-step episode-end
     probability of the built-in synthetic task (0: never terminates, like tasks/reacher.py).
 
     env: None for the built-in synthetic Reacher-shape task, or an object with
     ``reset(task) -> s0`` and ``step(task, a) -> (s1, phi, r, terminal)`` (numpy / floats),
-    called through C callbacks (agents/agent.py's Task interface: tasks/task.py).
+    called through C callbacks (agents/agent.py's Task interface: tasks/task.py).  Under the learned-φ
+    schedules the env's φ is not used and ``step`` may return None for it.
     """
 
     FIELDS = ("s", "s1", "phi", "a", "gamma", "snext", "phi1", "r1", "rb")
-    SCHEDULES = {"all": 0, "active": 1, "tsf": 2, "sharded": 3, "sharded_tsf": 4}
+    SCHEDULES = {"all": 0, "active": 1, "tsf": 2, "sharded": 3, "sharded_tsf": 4, "phi": 5, "tsf_phi": 6}
+    PHI_SCHEDULES = ("phi", "tsf_phi")
 
     def __init__(self, engine: SFEngine, batch: int = 32, capacity: int = 1_000_000, gamma: float = 0.9,
                  epsilon: float = 0.1, alpha_w: float = 1e-3, episode_len: int = 500, use_gpi: bool = True,
                  seed: int = 1, env=None, schedule: str = "all", upd_use_gpi: bool = True, p_end: float = 0.0,
-                 device_replay: bool = False):
+                 device_replay: bool = False, phi_bias=None, phi_lambda=None):
         import ctypes as C
 
         from ._lib import ENV_RESET_FN, ENV_STEP_FN, check, lib
@@ -253,6 +261,7 @@ class NativeEnvLoop:
         reset_fn = step_fn = None
         if env is not None:
             n_s, d = engine.n_s, engine.d
+            phi_unused = schedule in self.PHI_SCHEDULES
 
             def _reset(_ctx, task, s0):
                 try:
@@ -266,7 +275,10 @@ class NativeEnvLoop:
                 try:
                     ns, ph, rr, tt = env.step(task, a)
                     np.ctypeslib.as_array(s1, shape=(n_s,))[:] = np.asarray(ns, np.float32).reshape(n_s)
-                    np.ctypeslib.as_array(phi, shape=(d,))[:] = np.asarray(ph, np.float32).reshape(d)
+                    if ph is None and phi_unused:
+                        np.ctypeslib.as_array(phi, shape=(d,))[:] = 0.0
+                    else:
+                        np.ctypeslib.as_array(phi, shape=(d,))[:] = np.asarray(ph, np.float32).reshape(d)
                     r[0] = float(rr)
                     term[0] = 1 if tt else 0
                     return 0
@@ -285,8 +297,10 @@ class NativeEnvLoop:
         self.layout = {k: int(off[i]) for i, k in enumerate(self.FIELDS)}
         self.record_bytes = int(off[9])
         self.schedule = schedule
-        check(lib.sfx_runner_config(r, self.SCHEDULES[schedule], 1 if upd_use_gpi else 0, float(p_end)),
-              "sfx_runner_config")
+        self._phi_scalars = None
+        if phi_bias is not None or phi_lambda is not None:
+            self.set_phi_scalars(phi_bias, phi_lambda)
+        self.set_schedule(schedule, upd_use_gpi, p_end)
         self.task_index = 0
         if device_replay:
             self.set_device_replay(True)
@@ -295,6 +309,30 @@ class NativeEnvLoop:
         """SURVEY §8f rank 2 (opt-in; the north_star keeps the replay on the host): the ring in
         HBM, appended and sampled by each step's gate kernel; the host ring stays as a mirror."""
         self._check(self._lib.sfx_runner_device_replay(self._r, 1 if on else 0), "sfx_runner_device_replay")
+
+    def set_schedule(self, schedule: str, upd_use_gpi: bool = True, p_end: float = 0.0):
+        """sfx_runner_config: the training schedule of the next steps (between runs, before set_task)."""
+        self._check(self._lib.sfx_runner_config(self._r, self.SCHEDULES[schedule], 1 if upd_use_gpi else 0,
+                                                float(p_end)), "sfx_runner_config")
+        self.schedule = schedule
+
+    def set_phi_scalars(self, phi_bias, phi_lambda):
+        """The learned-φ schedules' per-task reward-model biases and loss coefficients (sfx_runner_phi_scalars):
+        contiguous float32 tensors of T elements on the engine's device, updated in place by the steps."""
+        e = self.eng
+        for name, t in (("phi_bias", phi_bias), ("phi_lambda", phi_lambda)):
+            if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == e.T
+                    and t.device == torch.device(e.device)):
+                raise ValueError(f"{name}: a contiguous float32 tensor of T = {e.T} elements on {e.device}")
+        self._check(self._lib.sfx_runner_phi_scalars(self._r, phi_bias.data_ptr(), phi_lambda.data_ptr()),
+                    "sfx_runner_phi_scalars")
+        self._phi_scalars = (phi_bias, phi_lambda)
+
+    def phi_losses(self):
+        """(loss, psi_loss, phi_loss, λ) of the last completed step that had an update (learned-φ schedules)."""
+        out = (self._C.c_float * 4)()
+        self._check(self._lib.sfx_runner_phi_losses(self._r, out), "sfx_runner_phi_losses")
+        return tuple(float(v) for v in out)
 
     def close(self):
         if getattr(self, "_r", None):

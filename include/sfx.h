@@ -358,7 +358,17 @@ int sfx_runner_layout(sfx_runner_t r, int64_t* offsets_host /* [10] */);
  * active task with the heads sharded over ranks (config C5, tsfdqn_nf.py:598-612: the active
  * policy's GPI maxima all-reduced, its owner updates, h and w_task handed to every rank by libsfx
  * collectives; needs sfx_tsf_setup, sfx_shard_setup and a communicator; the active task of
- * sfx_runner_set_task is then a global index).  use_gpi: next actions of the
+ * sfx_runner_set_task is then a global index), 5 the learned-φ SF agent (agents/sfdqn_phi.py:80-109
+ * over features/deep_phi.py: GPI with the active task's biased reward model q = ψ·w + b
+ * (DeepSF_PHI.GPI_w), ε-greedy, append -- the env callback's φ output is ignored, the staged φ rows
+ * stay in the record layout -- replay, DeepSF_PHI.update_successor of the active head, i.e. what
+ * sfx_phi_update does, bit for bit), 6 the learned-φ TSF agent (agents/tsfdqn_phi.py:80-103 over
+ * features/deep_tsf_phi.py: the same loop with TSFDQN_PHI.update_deep_models, sfx_tsf_phi_update's
+ * arithmetic).  Schedules 5 and 6 return SFX_E_STATE naming what is missing unless the handle is
+ * unsharded and has a φ net (sfx_phi_setup / sfx_phi_setup_dims), the runner has its per-task
+ * scalars (sfx_runner_phi_scalars), device replay is off and, for 6, the TSF state was made with
+ * G = d and K = 0; they pre-launch like schedule 1 but do not look ahead (sfx_runner_ahead_stats
+ * reports zero pre-steps).  use_gpi: next actions of the
  * update by GPI (1) or the own head (0).  p_end: episode-end probability per step of the
  * built-in synthetic task (γ = 0 on that transition; 0 = never, like tasks/reacher.py:112).
  * Call between runs (before sfx_runner_set_task). */
@@ -367,8 +377,17 @@ int sfx_runner_config(sfx_runner_t r, int schedule, int use_gpi, float p_end);
  * host, and so does the headline bench): the ring moves to HBM, each step hands the device only
  * its transition, and the step's gate kernel appends it and draws the uniform minibatch (index
  * function replay_index in csrc/sfx_kernels.h).  The host ring stays as a mirror (prefill,
- * records); switching uploads it before the next run.  Replaces agents/buffer.py:34-64. */
+ * records); switching uploads it before the next run.  Replaces agents/buffer.py:34-64.
+ * Refused with SFX_E_STATE under the learned-φ schedules (5, 6). */
 int sfx_runner_device_replay(sfx_runner_t r, int enable);
+/* The learned-φ schedules' per-task scalars: two caller-owned device arrays of T floats, element t
+ * task t's reward-model bias (fit_w[t].bias) and loss coefficient λ_t (agents/sfdqn_phi.py:62-70).
+ * The steps read and update them in place under the ownership contract of sfx_phi_update's
+ * bias_dev / lambda_dev; they must outlive the runner.  Call before sfx_runner_config(5 | 6). */
+int sfx_runner_phi_scalars(sfx_runner_t r, float* bias_dev, float* lambda_dev);
+/* (loss, psi_loss, phi_loss, λ after) of the last completed step that had an update -- what the agents
+ * log every step (agents/sfdqn_phi.py:104-109).  Between runs, learned-φ schedules only. */
+int sfx_runner_phi_losses(sfx_runner_t r, float* out_host /* [4] */);
 /* Agent.set_active_training_task (agents/agent.py:121-139): reset the env, select the first action */
 int sfx_runner_set_task(sfx_runner_t r, int task);
 /* n random transitions into the replay (warm-up; not env steps) */
@@ -407,7 +426,8 @@ int sfx_runner_retried(sfx_runner_t r, long long* retried);
  * activations, so step E+1 opens with its TD launch (its gate resets the speculation flag and runs
  * the LMS fit).  pre_steps: steps that started so; own_forward_steps: steps with an update that ran
  * their own forward (their minibatch sampled the slot of their own transition, whose next state
- * was unknown a step early; the first step of a run; after a target sync or a drain). */
+ * was unknown a step early; the first step of a run; after a target sync or a drain).  The
+ * learned-φ schedules (5, 6) do not look ahead: both counts stay zero. */
 int sfx_runner_ahead_stats(sfx_runner_t r, long long* pre_steps, long long* own_forward_steps);
 /* Steps whose host rounds found later steps cancelled at their gates: those steps' launches ran
  * (committing nothing) over the transient buffers the rounds read, so the step's forward and
