@@ -251,18 +251,21 @@ def td_grad(c: torch.Tensor, actions: torch.Tensor, targets: torch.Tensor, huber
 
 def sf_update(st: SFState, batch, i: int, *, use_gpi: bool = True, lr_sf: float = 1e-3,
               lr_w: float = 1e-3, wd_sf: float = 0.0, wd_w: float = 0.0,
-              target_update_ev: int = 1000, train_w: bool = True, huber: float = 0.0):
+              target_update_ev: int = 1000, train_w: bool = True, huber: float = 0.0, next_actions=None):
     """DeepSF.update_successor of sfdqn.py:303-371 (== features/deep_sequential.py:163-231).
 
     batch = (s [B,n_s], a [B] int64, r [B,1], phi [B,d], s1 [B,n_s], gamma [B]).
-    Mutates st; returns (loss, l1, l2, next_actions)."""
+    Mutates st; returns (loss, l1, l2, next_actions).  next_actions: use these instead of the argmax
+    (a float64 replay following an fp32 run's actions)."""
     s, a, r, phi, s1, gamma = batch
     spec = st.spec
     gamma = gamma.reshape(-1, 1)
     B = s.shape[0]
     idx = torch.arange(B)
     w_i = st.w[i]
-    if use_gpi:
+    if next_actions is not None:
+        next_actions = torch.as_tensor(next_actions)
+    elif use_gpi:
         q1, _ = gpi_w(psi_all(st.online, spec, s1), w_i)
         next_actions = gpi_next_actions(q1)
     else:
@@ -287,18 +290,22 @@ def sf_update(st: SFState, batch, i: int, *, use_gpi: bool = True, lr_sf: float 
     return l1 + l2, l1, l2, next_actions
 
 
-def deep_update(st: SFState, batch, i: int, *, lr: float = 1e-3, target_update_ev: int = 1000, huber: float = 0.0):
+def deep_update(st: SFState, batch, i: int, *, lr: float = 1e-3, target_update_ev: int = 1000, huber: float = 0.0,
+                next_actions=None):
     """features/deep.py:93-131 (the main_sfdqn_torch.py path): GPI next actions always,
     loss = l1 only, Adam over ψ_i only (the lambda's optimizer), w_i = LMS w [d].
 
-    batch = (s, a, phi, s1, gamma) (agents/buffer.py:34-60 layout)."""
+    batch = (s, a, phi, s1, gamma) (agents/buffer.py:34-60 layout).  next_actions: use these instead of the argmax."""
     s, a, phi, s1, gamma = batch
     spec = st.spec
     gamma = gamma.reshape(-1, 1)
     B = s.shape[0]
     idx = torch.arange(B)
-    q1, _ = gpi_w(psi_all(st.online, spec, s1), st.w[i])
-    next_actions = gpi_next_actions(q1)
+    if next_actions is not None:
+        next_actions = torch.as_tensor(next_actions)
+    else:
+        q1, _ = gpi_w(psi_all(st.online, spec, s1), st.w[i])
+        next_actions = gpi_next_actions(q1)
     c, xs = forward(st.online[i], spec, s)
     tpsi, _ = forward(st.target[i], spec, s1)
     targets = phi + gamma * tpsi[idx, next_actions, :]
@@ -313,10 +320,13 @@ def deep_update(st: SFState, batch, i: int, *, lr: float = 1e-3, target_update_e
     return l1, next_actions
 
 
-def deep_all_task_step(st: SFState, batch, *, lr: float = 1e-3, target_update_ev: int = 1000, huber: float = 0.0):
+def deep_all_task_step(st: SFState, batch, *, lr: float = 1e-3, target_update_ev: int = 1000, huber: float = 0.0,
+                       next_actions=None):
     """agents/sfdqn.py:57-60: every head updated on the same minibatch, in index order
-    (each GPI sees the heads already updated earlier in the same step)."""
-    return [deep_update(st, batch, i, lr=lr, target_update_ev=target_update_ev, huber=huber) for i in range(st.T)]
+    (each GPI sees the heads already updated earlier in the same step).  next_actions: one set per head to
+    follow instead of the argmax."""
+    return [deep_update(st, batch, i, lr=lr, target_update_ev=target_update_ev, huber=huber,
+                        next_actions=None if next_actions is None else next_actions[i]) for i in range(st.T)]
 
 
 # --------------------------------------------------------------------------------------
