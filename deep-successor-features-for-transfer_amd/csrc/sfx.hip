@@ -254,6 +254,7 @@ struct sfx_handle {
   unsigned long long* skipc = nullptr;  // [0] policies checked, [1] skipped (rounds >= 1)
   bool skip_rounds = true;        // SFX_SKIP=0: every round recomputes every policy
   bool bwd_merge = true;          // SFX_BWD_MERGE=0: the layer-1 dX keeps its own backward launch (run_bwd)
+  int tdg_rows = 0;               // SFX_TDG_ROWS=16 / 32: the fused TD launch's row tile forced (0: run_bwd's rule)
   StepOut* dout = nullptr;  // device
   // set by the runner while it captures a step: the final k_ver (with action selection)
   // publishes to pub_res instead of a separate k_publish; pub_folded reports that it did
@@ -697,8 +698,8 @@ int run_bwd(sfx_handle* h, int head0, int nhead, int M, const float* x0, const f
   const bool fuse = can_fuse_tdg(h) && ((uintptr_t)phi & 15) == 0 &&  // fused K2 reads φ rows as float4
                     (!td.xmax || 32 * h->A <= 1024);                     // and up to 4 maxima per thread
   if (!fuse && td.xi_dst) SFX_FAIL(SFX_E_STATE, "run_bwd: maxima re-initialisation needs the fused TD launch");
-  // round skipping: decided in the fused TD launch (M <= 32: one row tile per policy) or, unfused,
-  // by the TD launch's per-policy arrivals (tdg_skip_report)
+  // round skipping: decided in the fused TD launch (M <= 32: one row tile per policy votes, two
+  // 16-row tiles report through tdg_skip_report) or, unfused, by the TD launch's per-policy arrivals
   const bool armed = td.skip && (fuse ? M <= 32 : true);
   if (!fuse)
     RC(run_tdg(h, head0, nhead, td.guess, M, td.use_gpi, td.a, phi, td.gamma, td.next, td.next_stride, td.flag,
@@ -774,10 +775,24 @@ int run_bwd(sfx_handle* h, int head0, int nhead, int M, const float* x0, const f
     A.xi_src = td.xi_src;
     A.xi_dst = td.xi_dst;
     A.ra = geo(l);
-    A.na = cdiv(M, 32) * cdiv(h->L[l].K, 16);
+    // Row tile: 32 rows, or 16 where two row tiles per policy still leave every workgroup a CU of
+    // its own -- each then loads and reduces half the ψ rows of the policy's GPI (tdg_rows).  The
+    // many-head callers only: the single-head ones (active-task schedule, the TSF agents) keep 32
+    // rows.  SFX_TDG_ROWS = 16 forces it wherever 16 < M <= 32, 32 switches it off.
+    const int ktiles = cdiv(h->L[l].K, 16);
+    const bool rows16 = M > 16 && M <= 32 && h->tdg_rows != 32 &&
+                        (h->tdg_rows == 16 || (nhead > 1 && !ex.ride && nhead * 2 * ktiles <= h->ncu));
+    const int ntd = cdiv(M, rows16 ? 16 : 32) * ktiles;
+    A.na = ntd;
+    // the round that bumps the Adam step: one workgroup past the tiles for the heads' constants
+    dim3 grid = grid_of(ntd);
+    if (A.inc_step) A.adam_wg = (int)grid.x++ + 1;
     const double tdg_bytes = 4.0 * nhead * M * ((td.use_gpi ? h->T : 1) * h->O + 2.0 * h->O + 2.0 * h->d + 4);
-    launch(h, K_BWD, nhead * dx_bytes(l) + tdg_bytes, tdg_variant(h) == 1 ? k_bwd_tdg<2, 8> : k_bwd_tdg<4, 4>,
-           grid_of(A.na), dim3(256), h->G, A);
+    const bool v1 = tdg_variant(h) == 1;
+    launch(h, K_BWD, nhead * dx_bytes(l) + tdg_bytes,
+           rows16 ? (v1 ? k_bwd_tdg<2, 4, 16> : k_bwd_tdg<4, 2, 16>) : (v1 ? k_bwd_tdg<2, 8> : k_bwd_tdg<4, 4>), grid,
+           dim3(256), h->G, A);
+    A.adam_wg = 0;
     A.tdg = 0;
     A.xi_src = nullptr;
     A.xi_dst = nullptr;
@@ -1516,6 +1531,9 @@ int sfx_create(sfx_t* out, int T, int n_s, int H, int n_hidden, const int* acts,
   h->skip_rounds = !(esk && esk[0] == '0');
   const char* ebm = std::getenv("SFX_BWD_MERGE");
   h->bwd_merge = !(ebm && ebm[0] == '0');
+  const char* etr = std::getenv("SFX_TDG_ROWS");
+  const int tr = etr ? std::atoi(etr) : 0;
+  h->tdg_rows = tr == 16 || tr == 32 ? tr : 0;
   int off = 0, ptorch = 0;
   for (int l = 0; l < h->NL; ++l) {
     LayerGeo Lr{};
@@ -2044,6 +2062,15 @@ int sfx_graph_stats(sfx_t h, long long* captures, long long* launches, long long
   if (captures) *captures = h->graph_captures;
   if (launches) *launches = h->graph_launches + h->graph_eager;
   if (cached) *cached = (long long)h->graphs.size();
+  return SFX_OK;
+}
+
+int sfx_debug_spec_next(sfx_t h, int rows, int64_t* out_host) {
+  if (!h || !out_host || rows < 1 || rows > MMAX) SFX_FAIL(SFX_E_ARG, "bad args");
+  RC(settle(h));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  HIPCHK(hipMemcpy2D(out_host, sizeof(int64_t) * rows, h->spec_next, sizeof(int64_t) * MMAX, sizeof(int64_t) * rows,
+                     2 * (size_t)h->T, hipMemcpyDeviceToHost));
   return SFX_OK;
 }
 

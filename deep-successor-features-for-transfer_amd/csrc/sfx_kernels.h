@@ -1184,8 +1184,11 @@ struct RoleGeo {
 struct BwdArgs {
   int M, na, nb, nc, tail, head0, train_w, inc_step;
   int xcd, nhead;               // xcd: 1-D XCD-aware grid (xcd_decode) over nhead heads
-  int step_in_tail;             // 1: the tail bumps the Adam step; 0: dX tile 0 of this launch does
-  int tdg, tdg_use_gpi, tdg_guess, tdg_next_stride, flag_value, pad2_;  // fused TD target (K2)
+  int step_in_tail;             // 1: the tail bumps the Adam step; 0: the fused TD launch does (adam_wg)
+  int tdg, tdg_use_gpi, tdg_guess, tdg_next_stride, flag_value;  // fused TD target (K2)
+  // fused TD launch of a round that bumps the Adam step: 1 + blockIdx.x of the workgroup appended
+  // to its grid for the step counters and Adam constants of the launch's heads; 0: none
+  int adam_wg;
   const int64_t* tdg_a;
   const float* tdg_gamma;
   int64_t* tdg_next;
@@ -1241,27 +1244,35 @@ __device__ __forceinline__ const float* layer_input(const Geo& G, const BwdArgs&
   return xOff < 0 ? A.x0 : G.actp(R_S, head, xOff);
 }
 
-// K2 fused into the first backward launch: the TD target and output gradient of the 32 rows
-// m0.. of policy `pol` (the arithmetic of k_tdg, in the same order), left in LDS (s.dz, row
-// stride O) for this tile's dX.  The k-tile 0 workgroup of each row tile also publishes dZ,
+// K2 fused into the first backward launch: the TD target and output gradient of the RT (32 or
+// 16) rows m0.. of policy `pol` (the arithmetic of k_tdg, in the same order), left in LDS (s.dz,
+// row stride O) for this tile's dX.  The k-tile 0 workgroup of each row tile also publishes dZ,
 // the per-row losses and the next actions for the later launches.
 // Every global load is issued in stage A (one memory latency); stages B-E run from LDS.
-// Shapes (can_fuse_tdg): d = 4V <= 4 VMAX, 32·T·A <= 256 U, A·d <= 128.
+// Every item of stages B-E belongs to one row, so a row's bits do not depend on RT.
+// Shapes (can_fuse_tdg): d = 4V <= 4 VMAX, RT·T·A <= 256 U, A·d <= 128.
 constexpr int TDG_ROWS_O = 128;  // max A*d of a fused row tile
+template <int RT>
 struct TdgSmem {
-  float w[32], gam[32], ph[32 * 16];
-  int a[32], n[32];
-  float q[2048], m[32 * 128];
-  float tt[32 * TDG_ROWS_O], tc[32 * TDG_ROWS_O];
-  float dz[32 * TDG_ROWS_O];
+  float w[32], gam[RT], ph[RT * 16];
+  int a[RT], n[RT];
+  float q[RT * 64], m[RT * 128];
+  float tt[RT * TDG_ROWS_O], tc[RT * TDG_ROWS_O];
+  float dz[RT * TDG_ROWS_O];
 };
 
 // Returns 1 when the policy repeats the previous round's update (BwdArgs::tdg_prev): then the
 // output gradient and the row losses are left as that round wrote them.
-template <int VMAX, int U>
-__device__ int tdg_rows(const Geo& G, const BwdArgs& A, int pol, int m0, bool pub, TdgSmem& sm) {
+// A tile that does not hold every row of its policy (16 < M <= 32 at RT = 16) cannot decide that
+// alone: its publishing workgroup reports its rows' verdict (tdg_skip_report, one report per row
+// tile), the last report sets skip[pol] for the later launches, and the tile itself never returns
+// early -- for a policy that ends up skipped it rewrites what round r-1 wrote, with the same values.
+template <int VMAX, int U, int RT>
+__device__ int tdg_rows(const Geo& G, const BwdArgs& A, int pol, int m0, bool pub, TdgSmem<RT>& sm) {
+  static_assert(RT == 32 || RT == 16, "row tile of the fused TD launch");
+  constexpr int U4 = RT / 8;  // float4s (ints) per thread of an [RT][<= 128] block
   const int tid = threadIdx.x, T = G.T, Aa = G.A, d = G.d, O = G.O, NLm = G.lastOff, M = A.M;
-  const int nb = M - m0 < 32 ? M - m0 : 32;
+  const int nb = M - m0 < RT ? M - m0 : RT;
   const bool xm = A.tdg_xmax != nullptr;
   const int t0 = A.tdg_use_gpi ? 0 : pol, nt = A.tdg_use_gpi ? T : 1, TA = nt * Aa, n = xm ? 0 : nb * TA, V = d >> 2;
   const int guess = A.tdg_guess;
@@ -1281,9 +1292,9 @@ __device__ int tdg_rows(const Geo& G, const BwdArgs& A, int pol, int m0, bool pu
   const int n4 = (nb * O) >> 2;  // row tiles are whole float4s (O % 4 == 0)
   const float4* tg4 = reinterpret_cast<const float4*>(G.actp(R_S1T, pol, NLm) + (size_t)m0 * O);
   const float4* cu4 = reinterpret_cast<const float4*>(G.actp(R_S, pol, NLm) + (size_t)m0 * O);
-  float4 tt[4], tc[4];
+  float4 tt[U4], tc[U4];
 #pragma unroll
-  for (int u = 0; u < 4; ++u) {
+  for (int u = 0; u < U4; ++u) {
     const int i = tid + u * 256;
     tt[u] = i < n4 ? tg4[i] : make_float4(0.f, 0.f, 0.f, 0.f);
     tc[u] = i < n4 ? cu4[i] : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -1293,18 +1304,18 @@ __device__ int tdg_rows(const Geo& G, const BwdArgs& A, int pol, int m0, bool pu
   const float wk = tid < d ? G.w[(long long)pol * G.dpad + tid] : 0.f;
   const int ab_l = tid < nb ? (int)A.tdg_a[m0 + tid] : 0;
   const float gam_l = tid < nb ? A.tdg_gamma[m0 + tid] : 0.f;
-  int xv[4];  // raw sortable ints: decoded after the barrier, so no wait is placed here
+  int xv[U4];  // raw sortable ints: decoded after the barrier, so no wait is placed here
   if (xm) {  // the all-reduced maxima rows of this policy: stage C's output
     const int* xr = A.tdg_xmax + ((size_t)(A.tdg_poloff + pol) * M + m0) * Aa;
 #pragma unroll
-    for (int u = 0; u < 4; ++u) xv[u] = tid + u * 256 < nb * Aa ? xr[tid + u * 256] : 0;
+    for (int u = 0; u < U4; ++u) xv[u] = tid + u * 256 < nb * Aa ? xr[tid + u * 256] : 0;
   }
   // the previous round's next action of this thread's row, requested with the other operands
   // (stage D compares against it; a load there would cost a dependent round trip)
   const int64_t* prev = A.tdg_prev ? A.tdg_prev + (size_t)(pol - A.head0) * A.tdg_next_stride + m0 : nullptr;
   const int64_t prev_l = prev && tid < nb ? prev[tid] : -1;
 #pragma unroll
-  for (int u = 0; u < 4; ++u) {
+  for (int u = 0; u < U4; ++u) {
     const int i = tid + u * 256;
     if (i < n4) {
       reinterpret_cast<float4*>(sm.tt)[i] = tt[u];
@@ -1322,7 +1333,7 @@ __device__ int tdg_rows(const Geo& G, const BwdArgs& A, int pol, int m0, bool pu
   PROBE_AT(3);
   if (xm) {
 #pragma unroll
-    for (int u = 0; u < 4; ++u)
+    for (int u = 0; u < U4; ++u)
       if (tid + u * 256 < nb * Aa) sm.m[tid + u * 256] = unsortable(xv[u]);
   }
   // ---- stage B: q = ψ·w, one fmaf chain per dot in k order
@@ -1354,7 +1365,8 @@ __device__ int tdg_rows(const Geo& G, const BwdArgs& A, int pol, int m0, bool pu
   __syncthreads();
   PROBE_AT(6);
   // ---- stage D: first argmax over actions
-  int differs = prev == nullptr || m0 != 0 || nb != M;  // skipping needs every row of the policy
+  const bool whole = m0 == 0 && nb == M;  // this tile holds every row of the policy
+  int differs = prev == nullptr;
   for (int bl = tid; bl < nb; bl += 256) {
     const float* mb = sm.m + bl * Aa;
     int am = 0;
@@ -1370,15 +1382,20 @@ __device__ int tdg_rows(const Geo& G, const BwdArgs& A, int pol, int m0, bool pu
             A.tdg_next_stride);
     if (pub && A.tdg_next) A.tdg_next[(size_t)(pol - A.head0) * A.tdg_next_stride + m0 + bl] = am;
   }
-  const int same = !__syncthreads_or(differs);
-  if (pub && A.skip && tid == 0) {
-    A.skip[pol] = same;
-    if (A.skipc && prev) {
-      atomicAdd(A.skipc, 1ull);
-      if (same) atomicAdd(A.skipc + 1, 1ull);
+  const int any = __syncthreads_or(differs);
+  if (whole) {  // block-uniform vote
+    const int same = !any;
+    if (pub && A.skip && tid == 0) {
+      A.skip[pol] = same;
+      if (A.skipc && prev) {
+        atomicAdd(A.skipc, 1ull);
+        if (same) atomicAdd(A.skipc + 1, 1ull);
+      }
     }
+    if (same) return 1;
+  } else if (pub && A.skip && tid == 0) {  // one report per row tile; the tile goes on either way
+    tdg_skip_report(A.skip, A.skipc, pol, T, any != 0, prev != nullptr, (M + RT - 1) / RT);
   }
-  if (same) return 1;
   PROBE_AT(4);
   // ---- stage E: output gradient rows -- nonzero only at the taken action: one thread per
   // (row, feature) of it -- and the rows' squared errors (into sm.q, free after stage C)
@@ -1495,9 +1512,15 @@ __device__ __forceinline__ floatx4 dx_red_sum(const floatx4 (*red)[2][64], int s
   return v;
 }
 
-template <bool TDG, int VMAX = 2, int U = 8, bool BF = false>
+// RT: rows of a tile -- 32 (two 16-row accumulator blocks), or 16 in the fused TD launch where that
+// fills the chip (run_bwd): one block, the second block's loads, MFMAs, reduction and stores gone.
+// Rows m0 + 16.. of a 32-row tile and rows m0.. of the 16-row tile at the same m0 + 16 go through
+// the same MFMA chain and the same dx_red_sum order: the same bits.
+template <bool TDG, int VMAX = 2, int U = 8, bool BF = false, int RT = 32>
 __device__ __forceinline__ void role_dx(const Geo& G, const BwdArgs& A, int head, int tile, floatx4 (*red)[2][64]) {
   static_assert(!(BF && TDG), "bf16 dX: the plain dX tiles only (the fused TD launch stays fp32)");
+  static_assert(RT == 32 || (RT == 16 && TDG), "16-row tiles: the fused TD launch only");
+  constexpr int NRED = RT * 4;  // threads of the reduction: one per (16-row block, 4 rows, column)
   const RoleGeo L = A.ra;
   const int N = L.N, K = L.K, M = A.M;
   const int ntk = (K + 15) >> 4;
@@ -1506,17 +1529,17 @@ __device__ __forceinline__ void role_dx(const Geo& G, const BwdArgs& A, int head
   tile = TDG ? tile : tile / A.dxs;
   const int nchunk = ((N + A.dxs - 1) / A.dxs + 63) & ~63;
   const int nbeg = split * nchunk, nend = min(N, nbeg + nchunk);
-  const int k0 = (tile % ntk) * 16, m0 = (tile / ntk) * 32;
+  const int k0 = (tile % ntk) * 16, m0 = (tile / ntk) * RT;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, r = lane & 15, g = lane >> 4;
   const float* W = G.online + G.slot_off(rslot(A.mask, head), head) + L.wOff;
   const float* Xin = layer_input(G, A, head, L.xOff);
   float* out = G.dzp(head, L.dzIn);
   const int ma = m0 + r, mb = m0 + 16 + r, kk = k0 + r;
-  const bool oka = ma < M, okb = mb < M, okk = kk < K;
+  const bool oka = ma < M, okb = RT == 32 && mb < M, okk = kk < K;
   // activation outputs the reducing threads will need
   const int s = (threadIdx.x >> 6) & 1, Lx = threadIdx.x & 63, col = k0 + (Lx & 15);
   float xin[4] = {0.f, 0.f, 0.f, 0.f};
-  if (threadIdx.x < 128 && col < K) {
+  if (threadIdx.x < NRED && col < K) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int row = m0 + 16 * s + (Lx >> 4) * 4 + i;
@@ -1526,13 +1549,7 @@ __device__ __forceinline__ void role_dx(const Geo& G, const BwdArgs& A, int head
   floatx4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
   if constexpr (TDG) {
     // N = A*d <= 128: at most one 64-wide chunk per wave; its W slice is fetched before K2
-    __shared__ TdgSmem sm;
-    if (tile == 0 && A.inc_step && threadIdx.x == 0 && !step_cancelled(G.cancel)) {  // no dW reads them in this launch
-      const int st = G.step[head] + 1;
-      const AdamC ac = adam_consts(A.hp, st);
-      G.step[head] = st;
-      G.adamc[head] = ac;
-    }
+    __shared__ TdgSmem<RT> sm;
     if (A.flag && tile == 0 && head == A.head0 && threadIdx.x == 0) *A.flag = A.flag_value;
     // the 16 k-steps of each 64-wide chunk are split over the waves (4 or 8 steps each); the
     // partial sums meet in the reduction below
@@ -1542,15 +1559,15 @@ __device__ __forceinline__ void role_dx(const Geo& G, const BwdArgs& A, int head
 #pragma unroll
     for (int j = 0; j < 16; ++j)
       bw[j] = (j >= j0 && j < j0 + jw && okk && nb + j < N) ? W[(size_t)(nb + j) * K + kk] : 0.f;
-    if (tdg_rows<VMAX, U>(G, A, head, m0, tile % ntk == 0, sm)) return;  // repeats round r-1 (block-uniform)
+    if (tdg_rows<VMAX, U, RT>(G, A, head, m0, tile % ntk == 0, sm)) return;  // repeats round r-1 (block-uniform)
     const float* da = sm.dz + (size_t)r * N + nb;
-    const float* db = sm.dz + (size_t)(16 + r) * N + nb;
+    const float* db = sm.dz + (size_t)(RT == 32 ? 16 + r : r) * N + nb;  // (16 rows: in bounds, unused)
 #pragma unroll
     for (int j = 0; j < 16; ++j) {
       if (j >= j0 && j < j0 + jw) {
         const bool okj = nb + j < N;
         acc0 = mfma4(oka && okj ? da[j] : 0.f, bw[j], acc0);
-        acc1 = mfma4(okb && okj ? db[j] : 0.f, bw[j], acc1);
+        if constexpr (RT == 32) acc1 = mfma4(okb && okj ? db[j] : 0.f, bw[j], acc1);
       }
     }
   } else {
@@ -1563,7 +1580,7 @@ __device__ __forceinline__ void role_dx(const Geo& G, const BwdArgs& A, int head
   }
   PROBE_MARK();
   red[wave][0][lane] = acc0;
-  red[wave][1][lane] = acc1;
+  if constexpr (RT == 32) red[wave][1][lane] = acc1;
   __syncthreads();
   if (!TDG && A.dxs > 1) {  // partial tile -> dxpart; the last of the dxs splits finishes it
     const int ntile = ((M + 31) >> 5) * ntk;
@@ -1606,7 +1623,7 @@ __device__ __forceinline__ void role_dx(const Geo& G, const BwdArgs& A, int head
     }
     return;
   }
-  if (threadIdx.x < 128) {
+  if (threadIdx.x < NRED) {
     const floatx4 v = dx_red_sum(red, s, Lx);
     if (col < K) {
 #pragma unroll
@@ -2130,21 +2147,40 @@ __global__ __launch_bounds__(256) void k_bwd_mg(Geo G, BwdArgs A) {
   bwd_body<BF, true>(G, A, head + A.head0, bx, red);
 }
 
-// First backward launch with K2 fused: dX of the last layer only (A.na tiles per head).
-template <int VMAX, int U>
+// First backward launch with K2 fused: dX of the last layer only (A.na tiles per head, RT rows
+// each).  In the round that bumps the Adam step (BwdArgs::inc_step) the grid has one workgroup
+// more, past the tiles (BwdArgs::adam_wg): lane i bumps the step counter of head head0 + i and
+// writes its Adam constants -- two double pow, a sqrt and a division that no tile of this launch
+// waits for; the later launches of the round read them across the kernel boundary.  One writer
+// per head, nothing committed in a cancelled step.
+template <int VMAX, int U, int RT = 32>
 __global__ __launch_bounds__(256) void k_bwd_tdg(Geo G, BwdArgs A) {
   __shared__ floatx4 red[4][2][64];
   PROBE_T(pt0);
   if (A.xi_dst)
     fill_sortable(A.xi_dst, A.xi_src, A.xi_copy, A.xi_n, (blockIdx.y * gridDim.x + blockIdx.x) * 256 + threadIdx.x,
                   gridDim.x * gridDim.y * 256);
+  if (A.adam_wg && (int)blockIdx.x == A.adam_wg - 1) {
+    PROBE_MARKA();
+    if (!step_cancelled(G.cancel)) {
+      for (int i = threadIdx.x; i < A.nhead; i += 256) {
+        const int hd = A.head0 + i, st = G.step[hd] + 1;
+        const AdamC ac = adam_consts(A.hp, st);
+        G.step[hd] = st;
+        G.adamc[hd] = ac;
+      }
+    }
+    PROBE_MARK();
+    PROBE_REC(20, pt0);
+    return;
+  }
   int head = A.head0 + blockIdx.y, bx = blockIdx.x;
   if (A.xcd) {
     if (!xcd_decode(blockIdx.x, A.nhead, A.na, head, bx)) return;
     head += A.head0;
   }
   PROBE_MARKA();
-  role_dx<true, VMAX, U>(G, A, head, bx, red);
+  role_dx<true, VMAX, U, false, RT>(G, A, head, bx, red);
   PROBE_REC(3, pt0);
 }
 

@@ -587,6 +587,13 @@ class SFEngine:
         check(lib.sfx_skip_stats(self._h, C.byref(c), C.byref(s), int(reset)), "sfx_skip_stats")
         return {"policies_checked": c.value, "policies_skipped": s.value}
 
+    def debug_spec_next(self, rows: int) -> torch.Tensor:
+        """Test hook (sfx_debug_spec_next): the next actions the speculative rounds of the last fused
+        step published, int64 [2, T, rows] -- [0] the even rounds' buffer, [1] the odd rounds'."""
+        out = np.empty((2, self.T, int(rows)), dtype=np.int64)
+        check(lib.sfx_debug_spec_next(self._h, int(rows), out.ctypes.data), "sfx_debug_spec_next")
+        return torch.from_numpy(out)
+
     def lms(self, t: int, phi, r, alpha: float):
         if self._on_dev(phi, torch.float32) and phi.numel() == self.d and isinstance(r, (float, int)):
             # a device φ and a host reward (the reference agents' call): r as a kernel argument

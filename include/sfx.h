@@ -248,6 +248,11 @@ int sfx_step_stats(sfx_t h, long long* steps, long long* fallbacks, long long* r
  * would repeat bit for bit): policies checked and skipped so far, counted on the device
  * (synchronises the handle's stream); reset != 0 zeroes the counters afterwards. */
 int sfx_skip_stats(sfx_t h, long long* checked, long long* skipped, int reset);
+/* Test hook: the next actions that the speculative rounds of the last fused step published, rows
+ * 0 .. rows-1 of every policy, as out_host[2][T][rows] -- [0] the even rounds' buffer, [1] the odd
+ * rounds' (a step of two device rounds and no host round leaves round 0 in [0] and round 1 in
+ * [1]).  Settles the pending step and synchronises the handle's stream. */
+int sfx_debug_spec_next(sfx_t h, int rows, int64_t* out_host);
 /* Launch-graph cache of the handle: graphs captured (and instantiated) so far, graph launches,
  * graphs currently cached.  A call whose device pointers or configuration the cache has not seen
  * captures a new graph; a steady loop should capture only while it warms up. */
