@@ -419,7 +419,8 @@ class TSFState(SFState):
 
 
 def tsf_update(st: TSFState, batch, i: int, *, use_gpi: bool = True, beta: float = 1.0,
-               lr_sf=1e-3, lr_w=1e-3, lr_g=1e-3, lr_h=1e-3, target_update_ev: int = 1000, next_actions=None):
+               lr_sf=1e-3, lr_w=1e-3, lr_g=1e-3, lr_h=1e-3, target_update_ev: int = 1000, next_actions=None,
+               wd_sf: float = 0.0, wd_w: float = 0.0, wd_g: float = 0.0, wd_h: float = 0.0):
     """TSFDQN.update_successor (tsfdqn.py:588-709; tsfdqn_nf.py identical with planar g).
 
     φ̃ = (h(g_i(s)) + h(g_i(s1))) ⊙ φ ; targets = φ̃ + γ ψ⁻_i(s1)[a'] carry gradient into g_i, h;
@@ -466,10 +467,10 @@ def tsf_update(st: TSFState, batch, i: int, *, use_gpi: bool = True, beta: float
     g_h = torch.cat([g_Wh.reshape(-1), g_bh])
     st.step[i] += 1
     k = st.step[i]
-    adam_(st.online[i], g_psi, st.m[i], st.v[i], k, lr_sf)
-    adam_(st.w[i], g_w, st.wm[i], st.wv[i], k, lr_w)
-    adam_(st.g[i], g_g, st.gm[i], st.gv[i], k, lr_g)
-    adam_(st.h, g_h, st.hm[i], st.hv[i], k, lr_h)
+    adam_(st.online[i], g_psi, st.m[i], st.v[i], k, lr_sf, weight_decay=wd_sf)
+    adam_(st.w[i], g_w, st.wm[i], st.wv[i], k, lr_w, weight_decay=wd_w)
+    adam_(st.g[i], g_g, st.gm[i], st.gv[i], k, lr_g, weight_decay=wd_g)
+    adam_(st.h, g_h, st.hm[i], st.hv[i], k, lr_h, weight_decay=wd_h)
     st.since_target[i] += 1
     if st.since_target[i] >= target_update_ev:
         st.target[i].copy_(st.online[i])

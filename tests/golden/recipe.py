@@ -187,14 +187,21 @@ AGENT_RUN_TSF = dict(seed=13, n_s=17, H=32, A=7, d=8, acts=("relu", "relu"), T_t
                      buffer=dict(n_samples=500, n_batch=8), task_terminal_every=7)
 
 
-def agent_run_tsf(DeepTSF, TSFDQN, ReplayBuffer, device, nf=False):
+# AGENT_RUN_TSF with every decay switched on (each different, wd p comparable to g on this problem) and fewer
+# samples: the tsfdqn_nf call log that carries the decays across the drop-in boundary.
+AGENT_RUN_TSF_WD = dict(AGENT_RUN_TSF, n_samples=16, n_test_ev=8,
+                        hp=dict(AGENT_RUN_TSF["hp"], weight_decay_sf=2e-2, weight_decay_w=0.3, weight_decay_g=0.15,
+                                weight_decay_h=0.1, weight_decay_omega=5e-2))
+
+
+def agent_run_tsf(DeepTSF, TSFDQN, ReplayBuffer, device, nf=False, wd=False):
     """Build and train the TSF agent of AGENT_RUN_TSF (nf: tsfdqn_nf.py's planar-flow g_i with
-    n_coupling_layers = 3); returns (agent, tasks, test_tasks, returns)."""
+    n_coupling_layers = 3; wd: AGENT_RUN_TSF_WD); returns (agent, tasks, test_tasks, returns)."""
     import random
 
     import numpy as np
 
-    c = dict(AGENT_RUN_TSF)
+    c = dict(AGENT_RUN_TSF_WD if wd else AGENT_RUN_TSF)
     if nf:
         c["hp"] = dict(c["hp"], n_coupling_layers=3)
         c["seed"] = 17

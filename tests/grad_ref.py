@@ -286,11 +286,12 @@ def sf_grads(st, spec, batch, i: int, use_gpi: bool = True, huber: float = 0.0, 
     return grads, _info(nxt, gap, pre, (cur[idx, a, :] - targets).detach(), huber)
 
 
-def adam_(p, g, m, v, step: int, lr: float, eps: float):
-    R.adam_(p, g, m, v, step, lr, eps=eps)
+def adam_(p, g, m, v, step: int, lr: float, eps: float, betas=(B1, B2), wd: float = 0.0):
+    R.adam_(p, g, m, v, step, lr, betas=betas, eps=eps, weight_decay=wd)
 
 
-def all_task_step(st, mom, spec, batch, lr: float, eps: float, huber: float = 0.0, next_actions=None):
+def all_task_step(st, mom, spec, batch, lr: float, eps: float, huber: float = 0.0, next_actions=None,
+                  betas=(B1, B2), wd: float = 0.0):
     """The all-task step (every head on the same minibatch, in order, each GPI over the heads already updated;
     l1 only).  st["online"] and mom = dict(m, v [T, P], step [T]) advance -> [(grads, Info)] per head."""
     s, a, phi, s1, gamma = batch
@@ -299,7 +300,7 @@ def all_task_step(st, mom, spec, batch, lr: float, eps: float, huber: float = 0.
         g, info = sf_grads(st, spec, (s, a, None, phi, s1, gamma), i, True, huber,
                            None if next_actions is None else next_actions[i])
         mom["step"][i] += 1
-        adam_(st["online"][i], g["psi"], mom["m"][i], mom["v"][i], mom["step"][i], lr, eps)
+        adam_(st["online"][i], g["psi"], mom["m"][i], mom["v"][i], mom["step"][i], lr, eps, betas, wd)
         out.append((g, info))
     return out
 
@@ -550,9 +551,12 @@ TSF_GROUPS = ("psi", "w", "g", "h")
 _TSF_KEYS = dict(psi="online", w="w", g="g", h="h")
 
 
-def tsf_oracles(K: int, B: int, use_gpi: bool, seed: int):
+def tsf_oracles(K: int, B: int, use_gpi: bool, seed: int, lr=None, wd=None, betas=(B1, B2), eps: float = EPS_PSI):
     """Two updates (policy 1 on batch 0, then policy 2 on batch 1) from zero moments -> per update
-    (ref64, ref32 through recipe 1, fp32 Info); both of a policy's first step, so m = (1-β1) g."""
+    (ref64, ref32 through recipe 1, fp32 Info); both of a policy's first step, so m = (1-β1) g.
+    lr, wd: per group of TSF_GROUPS (LR_PSI and no decay where not given); the gradients are read with the
+    default β1 whatever the step's betas."""
+    lr, wd = lr or {}, wd or {}
     spec, gs, st, batches, _ = tsf_problem(K, B, seed)
     s32, s64 = cast(st, F32), cast(st, F64)
     out = []
@@ -563,12 +567,13 @@ def tsf_oracles(K: int, B: int, use_gpi: bool, seed: int):
         for stx, g in ((s32, g32), (s64, g64)):   # the step itself: every policy's optimizer has its own moments
             for k in TSF_GROUPS:
                 p = stx[_TSF_KEYS[k]] if k == "h" else stx[_TSF_KEYS[k]][i]
-                adam_(p, g[k], torch.zeros_like(p), torch.zeros_like(p), 1, LR_PSI, EPS_PSI)
+                adam_(p, g[k], torch.zeros_like(p), torch.zeros_like(p), 1, lr.get(k, LR_PSI), eps, betas, wd.get(k, 0.0))
     return out
 
 
-def tsf_test_oracles(K: int, seed: int):
-    """sfx_tsf_test_update at step 1 and 2 (its own Adam state) -> per step (ref64, ref32 through recipe 1)."""
+def tsf_test_oracles(K: int, seed: int, wd_w: float = 0.0, wd_omega: float = 0.0):
+    """sfx_tsf_test_update at step 1 and 2 (its own Adam state) -> per step (ref64, ref32 through recipe 1);
+    wd_w, wd_omega: the decays of the two groups (they enter the moments the gradients are read from)."""
     spec, gs, st, _, test = tsf_problem(K, 7, seed)
     out = []
     tm = {}
@@ -579,8 +584,8 @@ def tsf_test_oracles(K: int, seed: int):
         for k, (s, a, r, phi, s1, a1) in enumerate(test["steps"]):
             g = tsf_test_grads(stx, spec, gs, w, om, s.to(dt), a, r, phi.to(dt), s1.to(dt), a1, **TSF_TEST_HYPER)
             prev = (mw.clone(), mo.clone())
-            adam_(w, g["w"], mw, vw, k + 1, LR_PSI, EPS_PSI)
-            adam_(om, g["omega"], mo, vo, k + 1, LR_PSI, EPS_PSI)
+            adam_(w, g["w"], mw, vw, k + 1, LR_PSI, EPS_PSI, wd=wd_w)
+            adam_(om, g["omega"], mo, vo, k + 1, LR_PSI, EPS_PSI, wd=wd_omega)
             om.clamp_(1e-7)
             res.append((g, dict(w=grad_from_moments(mw, prev[0]), omega=grad_from_moments(mo, prev[1]))))
         tm[dt] = res

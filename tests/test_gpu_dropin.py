@@ -18,7 +18,7 @@ import pytest
 import torch
 
 from tests.conftest import gpu_available
-from tests.golden.recipe import AGENT_RUN, AGENT_RUN_SEQ, AGENT_RUN_TSF, AgentTask, agent_psi_lambda
+from tests.golden.recipe import AGENT_RUN, AGENT_RUN_SEQ, AGENT_RUN_TSF, AGENT_RUN_TSF_WD, AgentTask, agent_psi_lambda
 from tests.test_gpu_engine import params_close, rel_close
 
 pytestmark = pytest.mark.gpu
@@ -58,8 +58,9 @@ def _build(stack, g):
     from sfx.dropin.features import deep, deep_sequential, deep_sequential_tsf
 
     tsf = stack.startswith("tsfdqn")
-    c = AGENT_RUN if stack == "sfdqn_alltask" else AGENT_RUN_SEQ if stack.startswith("sfdqn") else dict(AGENT_RUN_TSF)
-    if stack == "tsfdqn_nf":
+    c = AGENT_RUN if stack == "sfdqn_alltask" else AGENT_RUN_SEQ if stack.startswith("sfdqn") else \
+        dict(AGENT_RUN_TSF_WD if stack.endswith("_wd") else AGENT_RUN_TSF)
+    if stack.startswith("tsfdqn_nf"):
         c["hp"] = dict(c["hp"], n_coupling_layers=3)
     handle = agent_psi_lambda(c["H"], c["acts"], c["lr"], DEV)
     if stack == "sfdqn_alltask":
@@ -80,7 +81,7 @@ def _build(stack, g):
     T, n_s, d = c["T_tasks"], c["n_s"], c["d"]
     gfun, h = [], None
     if tsf:
-        G, K = c["hp"]["g_h_function_dims"], c["hp"].get("n_coupling_layers", 0) if stack == "tsfdqn_nf" else 0
+        G, K = c["hp"]["g_h_function_dims"], c["hp"].get("n_coupling_layers", 0) if stack.startswith("tsfdqn_nf") else 0
         h = torch.nn.Linear(G, d).to(DEV)
         _load(h, g["init.h"])
     for t in range(T):
@@ -112,7 +113,7 @@ def _w(x):
 
 
 STACKS = ["sfdqn_alltask", "sfdqn_sequential", "sfdqn_singlefile", "tsfdqn_sequential", "tsfdqn_singlefile",
-          "tsfdqn_nf"]
+          "tsfdqn_nf", "tsfdqn_nf_wd"]
 
 
 @pytest.mark.parametrize("stack", STACKS)

@@ -121,12 +121,14 @@ def batches_of(g):
             for j in range(int(g["k"]))]
 
 
-@pytest.mark.parametrize("case", ["sfdqn_gpi", "sfdqn_nogpi", "sfdqn_tanh"])
+@pytest.mark.parametrize("case", ["sfdqn_gpi", "sfdqn_nogpi", "sfdqn_tanh", "sfdqn_wd"])
 def test_update_vs_golden(golden, case):
     g = golden("upd_" + case)
     spec, T = spec_of(g), int(g["T"])
     eng = engine_for(spec, T)
-    eng.set_adam(1e-3, 0.0, 1e-3, 0.0)
+    wd_sf, wd_w = (float(g[n]) if n in g else 0.0 for n in ("wd_sf", "wd_w"))   # the *_wd fixtures record theirs
+    assert (wd_sf > 0 and wd_w > 0) == case.endswith("_wd")
+    eng.set_adam(1e-3, wd_sf, 1e-3, wd_w)
     eng.set_target_update_ev(int(g["target_update_ev"]))
     for t in range(T):
         eng.load_head(t, g["online0"][t], 0)

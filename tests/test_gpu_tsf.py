@@ -22,16 +22,19 @@ def _need_gpu():
         pytest.skip("no HIP device")
 
 
-@pytest.mark.parametrize("case", ["tsf", "tsf_nf"])
+@pytest.mark.parametrize("case", ["tsf", "tsf_nf", "tsf_nf_wd"])
 def test_tsf_update_vs_golden(golden, case):
     from sfx.engine import SFEngine
 
     g = golden("upd_" + case)
     spec, T = spec_of(g), int(g["T"])
     eng = SFEngine(T, spec.n_s, spec.H, spec.A, spec.d, spec.acts, max_batch=32)
-    eng.set_adam(1e-3, 0.0, 1e-3, 0.0)
+    # the *_wd fixtures record their decays
+    wd = {n: float(g["wd_" + n]) if "wd_" + n in g else 0.0 for n in ("sf", "w", "g", "h")}
+    assert all(v > 0 for v in wd.values()) == case.endswith("_wd")
+    eng.set_adam(1e-3, wd["sf"], 1e-3, wd["w"])
     eng.set_target_update_ev(int(g["target_update_ev"]))
-    eng.tsf_setup(int(g["G"]), int(g["K"]), float(g["beta"]), 1e-3, 0.0, 1e-3, 0.0)
+    eng.tsf_setup(int(g["G"]), int(g["K"]), float(g["beta"]), 1e-3, wd["g"], 1e-3, wd["h"])
     for t in range(T):
         eng.load_head(t, g["online0"][t], 0)
         eng.load_head(t, g["online0"][t], 1)

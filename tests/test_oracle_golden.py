@@ -69,16 +69,25 @@ def batches_of(g):
     return out
 
 
-@pytest.mark.parametrize("case", ["sfdqn_gpi", "sfdqn_nogpi", "sfdqn_tanh"])
+def decays_of(g, *names):
+    """The decays a *_wd fixture was generated with (tools/gen_golden.py gen_wd); zero where it records none."""
+    wd = {n: float(g[n]) if n in g else 0.0 for n in names}
+    assert all(v > 0 for v in wd.values()) or not any(wd.values())
+    return wd
+
+
+@pytest.mark.parametrize("case", ["sfdqn_gpi", "sfdqn_nogpi", "sfdqn_tanh", "sfdqn_wd"])
 def test_sf_update_matches_reference(golden, case):
     g = golden("upd_" + case)
     spec = spec_of(g)
+    wd = decays_of(g, "wd_sf", "wd_w")
+    assert any(wd.values()) == case.endswith("_wd")
     st = R.SFState(spec, torch.from_numpy(g["online0"]).clone(), torch.from_numpy(g["target0"]).clone(),
                    torch.from_numpy(g["w0"]).clone())
     for j, b in enumerate(batches_of(g)):
         i = int(g["policies"][j])
         loss, l1, l2, na = R.sf_update(st, b, i, use_gpi=bool(g["use_gpi"]),
-                                       target_update_ev=int(g["target_update_ev"]))
+                                       target_update_ev=int(g["target_update_ev"]), **wd)
         assert np.array_equal(na.numpy(), g["next_actions"][j])
         close([float(loss), float(l1), float(l2)], g["losses"][j], rtol=1e-5, atol=1e-7)
         if j == 0:
@@ -114,10 +123,12 @@ def test_deep_all_task_matches_reference(golden):
     assert list(st.since_target) == list(g["since_target"])
 
 
-@pytest.mark.parametrize("case", ["tsf", "tsf_nf"])
+@pytest.mark.parametrize("case", ["tsf", "tsf_nf", "tsf_nf_wd"])
 def test_tsf_update_matches_reference(golden, case):
     g = golden("upd_" + case)
     spec = spec_of(g)
+    wd = decays_of(g, "wd_sf", "wd_w", "wd_g", "wd_h")
+    assert any(wd.values()) == case.endswith("_wd")
     T = int(g["T"])
     gs = R.GSpec(spec.n_s, int(g["G"]), int(g["K"]))
     online0 = torch.from_numpy(g["online0"])
@@ -127,7 +138,7 @@ def test_tsf_update_matches_reference(golden, case):
     for j, b in enumerate(batches_of(g)):
         i = int(g["policies"][j])
         loss, l1, l2, _ = R.tsf_update(st, b, i, beta=float(g["beta"]),
-                                       target_update_ev=int(g["target_update_ev"]))
+                                       target_update_ev=int(g["target_update_ev"]), **wd)
         close([float(loss), float(l1), float(l2)], g["losses"][j], rtol=1e-5, atol=1e-7)
     close(st.online, g["online"], rtol=1e-4, atol=1e-6)
     close(st.target, g["target"], rtol=1e-4, atol=1e-6)

@@ -16,7 +16,8 @@ initial weights and outputs of:
 into small ``.npz`` fixtures under tests/golden/.  The fixtures are data only;
 this script never travels to the GPU box (it needs /root/reference).
 
-Usage:  python tools/gen_golden.py
+Usage:  python tools/gen_golden.py            every fixture
+        python tools/gen_golden.py gen_wd     only the named generators (here: the fixtures with the decays on)
 """
 from __future__ import annotations
 
@@ -151,10 +152,10 @@ def np_(t):
 
 
 # --------------------------------------------------------------------------------------
-def build_sfdqn(shape, T, target_update_ev=1000):
+def build_sfdqn(shape, T, target_update_ev=1000, hyper=None):
     n_s, H, A, d, acts = shape
     sf = ref_sfdqn.DeepSF(pytorch_model_handle=psi_lambda(H, acts), use_true_reward=False,
-                          target_update_ev=target_update_ev, hyperparameters=HYPER)
+                          target_update_ev=target_update_ev, hyperparameters=hyper or HYPER)
     sf.reset()
     for t in range(T):
         sf.add_training_task(SynthTask(n_s, A, d, t))
@@ -237,15 +238,27 @@ def gen_full_size():
     np.savez_compressed(os.path.join(OUT, "gpi_reacher17_full.npz"), **rec)
 
 
-def gen_sfdqn_updates(name, shape, T, k, use_gpi, target_update_ev):
+# the decays of the *_wd fixtures: wd p comparable to g on these problems, all different
+WD = {"weight_decay_sf": 2e-2, "weight_decay_w": 0.3, "weight_decay_g": 0.15, "weight_decay_h": 0.1}
+
+
+def decays_of(hyper):
+    return {"wd_" + k[len("weight_decay_"):]: float(hyper[k]) for k in WD}
+
+
+def gen_sfdqn_updates(name, shape, T, k, use_gpi, target_update_ev, hyper=None):
+    """hyper: overrides of HYPER (the decays); recorded in the fixture only when given, so that the fixtures
+    written without them stay byte-identical."""
     torch.manual_seed(200 + int(use_gpi))
-    sf = build_sfdqn(shape, T, target_update_ev)
+    sf = build_sfdqn(shape, T, target_update_ev, None if hyper is None else dict(HYPER, **hyper))
     n_s, H, A, d, acts = shape
     online0, target0, w0 = sfdqn_weights(sf)
     batches = batch_stream(n_s, A, d, 32, k, torch.Generator().manual_seed(3))
     rec = dict(n_s=n_s, H=H, A=A, d=d, T=T, acts=np.array(acts), k=k, use_gpi=int(use_gpi),
                target_update_ev=target_update_ev, online0=np_(online0), target0=np_(target0),
                w0=np_(w0), **stack_batches(batches))
+    if hyper is not None:
+        rec.update(decays_of(dict(HYPER, **hyper)))
     losses, nexts, policies = [], [], []
     for j, b in enumerate(batches):
         i = j % T
@@ -321,10 +334,10 @@ def gen_deep_alltask(shape, T, k, target_update_ev):
     np.savez_compressed(os.path.join(OUT, "upd_deep_alltask.npz"), **rec)
 
 
-def gen_tsf(name, module, shape, T, k, K):
+def gen_tsf(name, module, shape, T, k, K, hyper_over=None):
     torch.manual_seed(400 + K)
     n_s, H, A, d, acts = shape
-    hyper = dict(HYPER, n_coupling_layers=K)
+    hyper = dict(HYPER, n_coupling_layers=K, **(hyper_over or {}))
     sf = module.DeepTSF(pytorch_model_handle=psi_lambda(H, acts), use_true_reward=False,
                         target_update_ev=4, hyperparameters=hyper)
     agent = module.TSFDQN(deep_sf=sf, buffer_handle=lambda: None, gamma=0.9, T=500, encoding=None,
@@ -340,6 +353,8 @@ def gen_tsf(name, module, shape, T, k, K):
     rec = dict(n_s=n_s, H=H, A=A, d=d, T=T, acts=np.array(acts), k=k, K=K, G=hyper["g_h_function_dims"],
                beta=hyper["beta_loss_coefficient"], target_update_ev=4, online0=np_(online0),
                w0=np_(w0), g0=np_(g0), h0=np_(h0), **stack_batches(batches))
+    if hyper_over is not None:
+        rec.update(decays_of(hyper))
     losses, policies = [], []
     for j, b in enumerate(batches):
         i = j % T
@@ -601,7 +616,7 @@ def gen_call_log_sequential(single_file=False):
     log.save(os.path.join(OUT, name + ".npz"), _final(agent, log))
 
 
-def gen_call_log_tsf(nf=False, single_file=False):
+def gen_call_log_tsf(nf=False, single_file=False, wd=False):
     """main_tsfdqn_sequential_torch.py's stack (agents/tsfdqn_sequential.py +
     features/deep_sequential_tsf.py), the single-file tsfdqn.py, or tsfdqn_nf.py (planar flows)."""
     import contextlib
@@ -620,9 +635,17 @@ def gen_call_log_tsf(nf=False, single_file=False):
     log = CallLog()
     with contextlib.redirect_stdout(io.StringIO()):
         agent, *_ = agent_run_tsf(recording_sf(DeepTSF, log), recording_tsf_agent(TSFDQN, log), ReplayBuffer,
-                                  torch.device("cpu"), nf=nf)
+                                  torch.device("cpu"), nf=nf, wd=wd)
     name = "calls_tsfdqn_nf" if nf else "calls_tsfdqn_singlefile" if single_file else "calls_tsfdqn_sequential"
-    log.save(os.path.join(OUT, name + ".npz"), _final(agent, log))
+    log.save(os.path.join(OUT, name + ("_wd" if wd else "") + ".npz"), _final(agent, log))
+
+
+def gen_wd():
+    """Only the fixtures with the decays switched on (python tools/gen_golden.py gen_wd); every other fixture
+    stays as committed."""
+    gen_sfdqn_updates("sfdqn_wd", SHAPES["tanh_odd"], 3, 7, True, 3, hyper=WD)
+    gen_tsf("tsf_nf_wd", ref_tsfdqn_nf, SHAPES["reacher17"], 3, 6, 3, hyper_over=WD)
+    gen_call_log_tsf(nf=True, wd=True)
 
 
 def gen_call_logs():
@@ -653,6 +676,7 @@ def main():
     gen_tsf_tests()
     gen_phis()
     gen_call_logs()
+    gen_wd()
     print("golden vectors written to", os.path.abspath(OUT))
 
 
