@@ -40,6 +40,7 @@
 #include "sfx_phiw.h"
 #include "sfx_tsfphi.h"
 #include "sfx_phitest.h"
+#include "sfx_pre.h"
 #include "../../include/sfx.h"
 
 using namespace sfx;
@@ -2260,3 +2261,4 @@ int sfx_synchronize(sfx_t h) {
 #include "sfx_runner.inc"
 #include "sfx_tsf.inc"
 #include "sfx_phi.inc"
+#include "sfx_pre.inc"

@@ -143,6 +143,19 @@ SIGNATURES = {
     "sfx_tsf_test_update": (_I, [_VP, _VP, _VP, _VP, _VP, _F, _VP, _VP, _VP, _VP, _I] + [_F] * 7 + [_VP]),
     "sfx_tsf_test_actions": (_I, [_VP, _VP, _I, _VP, _I, _VP, _I, _VP]),
     "sfx_tsf_test_updates": (_I, [_VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, _I, _VP, _I, _VP, _I, _VP, _F, _F, _F, _VP]),
+    "sfx_pre_create": (_I, [C.POINTER(_VP), _I, _I, _I, _IP, _I, _I]),
+    "sfx_pre_destroy": (_I, [_VP]),
+    "sfx_pre_set_stream": (_I, [_VP, _VP]),
+    "sfx_pre_numel": (_I, [_VP]),
+    "sfx_pre_set_adam": (_I, [_VP, _D, _D, _D, _D, _D, _D, _D]),
+    "sfx_pre_load": (_I, [_VP, _FP]),
+    "sfx_pre_get": (_I, [_VP, _FP]),
+    "sfx_pre_load_adam": (_I, [_VP, _FP, _FP, _I]),
+    "sfx_pre_get_adam": (_I, [_VP, _FP, _FP, _IP]),
+    "sfx_pre_load_w": (_I, [_VP, _I, _FP, _FP, _FP, _I]),
+    "sfx_pre_get_w": (_I, [_VP, _I, _FP, _FP, _FP, _IP]),
+    "sfx_pre_update": (_I, [_VP, _I, _VP, _VP, _VP, _VP, _I, _VP]),
+    "sfx_pre_features": (_I, [_VP, _VP, _VP, _VP, _I, _VP]),
 }
 
 # env callbacks of sfx_runner_create (include/sfx.h)

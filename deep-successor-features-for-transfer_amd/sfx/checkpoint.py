@@ -38,6 +38,16 @@ main_tsfdqn_phi_torch.py's 2048) records ``{hid, n_mid, lr}`` as its configurati
 ``phi_setup*`` and ``tsf_setup(G = d, K = 0)``) carries both blocks, g_i and h next to φ (their
 persistent Adam moments are unused by that update and stay zero).
 
+A φ pre-training engine (sfx.pretrain.PreEngine; sfdqn_phi.py:800-873) has a checkpoint of its own
+(``pre_state_dict`` / ``load_pre_state_dict`` / ``save_pre`` / ``load_pre``, format ``sfx-pretrain-1``):
+
+* ``phi_model`` -- the state_dict of PhiFunction (sfdqn_phi.py:90-123): ``_model.{0,2,4}.{weight,bias}``;
+* ``phi_optim`` -- the state_dict of its ``torch.optim.Adam`` (:106), the one that lives for the whole phase:
+  per parameter ``step`` / ``exp_avg`` / ``exp_avg_sq`` (none before the first step);
+* ``rows[t]["w_model"]`` -- ``fit_w`` of task t, ``Linear(d, 1, bias=False)`` (:818-820): ``weight`` [1, d];
+  ``rows[t]["optim"]`` -- its own Adam (:822) with its own step count;
+* ``geometry`` (n_s, d, T, hidden), ``adam`` -- what the engine was built with.
+
 So a reference user resumes with ``model.load_state_dict(ck["heads"][t]["model"])`` and
 ``optim.load_state_dict(ck["heads"][t]["optim"])``, and an engine with ``load(eng, path)``.
 """
@@ -242,3 +252,85 @@ def save(eng, path: str) -> None:
 
 def load(eng, path: str) -> None:
     load_state_dict(eng, torch.load(path, weights_only=True))
+
+
+# ---------------------------------------------------------------------------------------------
+# φ pre-training (sfx.pretrain.PreEngine)
+# ---------------------------------------------------------------------------------------------
+PRE_FORMAT = "sfx-pretrain-1"
+
+
+def pre_shapes(n_s: int, d: int, hidden) -> List[Tuple[str, Tuple[int, ...]]]:
+    """PhiFunction's parameters in torch packing order: Linear j of the Sequential sits at index 2 j."""
+    widths = [2 * n_s + 1] + [int(h) for h in hidden] + [d]
+    out = []
+    for j in range(len(widths) - 1):
+        out += [(f"_model.{2 * j}.weight", (widths[j + 1], widths[j])), (f"_model.{2 * j}.bias", (widths[j + 1],))]
+    return out
+
+
+def _pre_geometry(eng) -> dict:
+    return {"n_s": eng.n_s, "d": eng.d, "T": eng.T, "hidden": list(eng.hidden)}
+
+
+def _pre_optim(hp: dict, lr: float, wd: float, step: int, ms, vs, names) -> dict:
+    state = _state_entries(step, ms, vs, names, 0) if step > 0 else {}
+    return {"state": state, "param_groups": [_adam_group({**hp, "lr_psi": lr, "wd_psi": wd}, len(names))]}
+
+
+def pre_state_dict(eng) -> dict:
+    """The pre-training state (host copies; synchronous): the φ net, the rows, every moment and step count."""
+    shapes = pre_shapes(eng.n_s, eng.d, eng.hidden)
+    names = [n for n, _ in shapes]
+    hp = eng.adam_hp
+    m, v, step = eng.get_adam()
+    rows = []
+    for t in range(eng.T):
+        w, wm, wv, wstep = eng.get_w(t)
+        rows.append({"w_model": OrderedDict(weight=w.reshape(1, -1).clone()),
+                     "optim": _pre_optim(hp, hp["lr_w"], hp["wd_w"], wstep, {"weight": wm.reshape(1, -1).clone()},
+                                         {"weight": wv.reshape(1, -1).clone()}, ["weight"])})
+    return {"format": PRE_FORMAT, "geometry": _pre_geometry(eng),
+            "adam": {k: (list(x) if isinstance(x, tuple) else x) for k, x in hp.items()},
+            "phi_model": unpack(eng.get(), shapes),
+            "phi_optim": _pre_optim(hp, hp["lr_phi"], hp["wd_phi"], step, unpack(m, shapes), unpack(v, shapes), names),
+            "rows": rows}
+
+
+def _pre_optim_state(optim: dict, shapes, what: str):
+    """(m, v, step) in packing order from an Adam state_dict; zeros and step 0 where torch keeps no state yet."""
+    st = optim["state"]
+    n = sum(int(torch.tensor(shp).prod()) for _, shp in shapes)
+    if not st:
+        return torch.zeros(n), torch.zeros(n), 0
+    steps = {int(round(float(st[i]["step"]))) for i in range(len(shapes))}
+    if len(steps) != 1:
+        raise ValueError(f"{what}: per-parameter Adam steps differ ({sorted(steps)})")
+    m = pack({name: st[i]["exp_avg"] for i, (name, _) in enumerate(shapes)}, shapes)
+    v = pack({name: st[i]["exp_avg_sq"] for i, (name, _) in enumerate(shapes)}, shapes)
+    return m, v, steps.pop()
+
+
+def load_pre_state_dict(eng, ck: dict) -> None:
+    """Restore a PreEngine of the same geometry from `ck`."""
+    if ck.get("format") != PRE_FORMAT:
+        raise ValueError(f"not an sfx pre-training checkpoint (format {ck.get('format')!r})")
+    if dict(ck["geometry"]) != _pre_geometry(eng):
+        raise ValueError(f"checkpoint geometry {ck['geometry']} does not match the engine's {_pre_geometry(eng)}")
+    hp = ck["adam"]
+    eng.set_adam(hp["lr_phi"], hp["wd_phi"], hp["lr_w"], hp["wd_w"], tuple(hp["betas"]), hp["eps"])
+    shapes = pre_shapes(eng.n_s, eng.d, eng.hidden)
+    eng.load(pack(ck["phi_model"], shapes))
+    eng.load_adam(*_pre_optim_state(ck["phi_optim"], shapes, "phi_optim"))
+    wsh = [("weight", (1, eng.d))]
+    for t, row in enumerate(ck["rows"]):
+        m, v, step = _pre_optim_state(row["optim"], wsh, f"rows[{t}]")
+        eng.load_w(t, pack(row["w_model"], wsh), m, v, step)
+
+
+def save_pre(eng, path: str) -> None:
+    torch.save(pre_state_dict(eng), path)
+
+
+def load_pre(eng, path: str) -> None:
+    load_pre_state_dict(eng, torch.load(path, weights_only=True))

@@ -12,6 +12,10 @@ unchanged on libsfx:
   library classes become sfx's and the TSF agents' ``update_successor`` one libsfx call;
   ``agents.sfdqn_phi`` and ``agents.tsfdqn_phi`` load as they are too, the latter's
   ``TSFDQN_PHI.update_deep_models`` becoming one libsfx call (sfx_tsf_phi_update);
+* the single-file learned-φ agents ``sfdqn_phi`` and ``tsfdqn_phi`` load as they are; their opening phase
+  ``SFDQN.pre_train`` / ``TSFDQN.pre_train`` becomes ``sfx.pretrain.pre_train`` (one libsfx call per
+  minibatch update, sfx_pre_update) and ``self.learnt_phi`` an ``sfx.pretrain.LearntPhi``; everything else in
+  those modules stays the user's;
 * ``agents.buffer`` is sfx's ``ReplayBuffer`` (the reference's API over a device-resident ring,
   the same ``np.random`` index draws; ``sfx/dropin/agents/buffer.py``);
 * every other ``agents`` module, ``utils``, ``tasks`` and the scripts themselves are the user's, untouched.
@@ -31,7 +35,8 @@ FEATURES = os.path.join(ROOT, "features")
 AGENT_ALIASES = {"agents.buffer": os.path.join(ROOT, "agents", "buffer.py")}
 OURS = ("features.deep", "features.deep_sequential", "features.deep_sequential_tsf", "features.deep_phi",
         "features.deep_tsf_phi", "features.successor")
-BOUND = ("sfdqn", "tsfdqn", "tsfdqn_nf", "agents.tsfdqn_sequential", "agents.sfdqn_phi", "agents.tsfdqn_phi")
+BOUND = ("sfdqn", "tsfdqn", "tsfdqn_nf", "agents.tsfdqn_sequential", "agents.sfdqn_phi", "agents.tsfdqn_phi",
+         "sfdqn_phi", "tsfdqn_phi")
 
 
 class _BindingLoader(importlib.abc.Loader):

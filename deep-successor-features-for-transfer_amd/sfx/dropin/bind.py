@@ -16,7 +16,10 @@ and loss coefficient (DeepSF_TSF_PHI.tsf_phi_test_action / tsf_phi_test_update);
 ``agents.sfdqn_phi``'s update_test_reward_mapper (:263-305) likewise (DeepSF_PHI.phi_test_update).
 Where the agent's modules are not the shapes the library runs, those methods fall back to the
 agent's own torch code, after the device's φ net, g_i and h are copied back into its modules -- as
-``test_agent`` is wrapped to do once per test episode.  Nothing else of the user's agents is touched.
+``test_agent`` is wrapped to do once per test episode.  The single-file learned-φ agents ``sfdqn_phi`` /
+``tsfdqn_phi`` keep everything but their opening phase: ``SFDQN.pre_train`` (sfdqn_phi.py:800-873) /
+``TSFDQN.pre_train`` (tsfdqn_phi.py:1036-1109) becomes ``sfx.pretrain.pre_train``.  Nothing else of the user's
+agents is touched.
 """
 from __future__ import annotations
 
@@ -229,6 +232,20 @@ def bind_phi_test(cls) -> None:
     cls.update_test_reward_mapper = update_test_reward_mapper
 
 
+def lib_pre_train(self, train_tasks, n_samples_pre_train, n_cycles=5):
+    """SFDQN.pre_train (sfdqn_phi.py:800-873) / TSFDQN.pre_train (tsfdqn_phi.py:1036-1109): the same loop and
+    RNG draws, every minibatch update one library call; ``self.learnt_phi`` becomes the frozen net on the device
+    (sfx.pretrain.LearntPhi, callable as PhiFunction.forward is).  Returns the losses as a list of floats."""
+    from .. import pretrain
+
+    self.learnt_phi, losses = pretrain.pre_train(train_tasks, n_samples_pre_train, n_cycles)
+    self.learnt_phi.set_eval()
+    return losses
+
+
+lib_pre_train.__sfx_bound__ = True
+
+
 def patch(name: str, module) -> None:
     """Bind the user's freshly loaded module ``name`` to sfx (see the module docstring)."""
     if name == "sfdqn":
@@ -244,6 +261,10 @@ def patch(name: str, module) -> None:
             module.SFDQN_PHI.test_agent = _phi_synced(m)
         if hasattr(module.SFDQN_PHI, "update_test_reward_mapper"):
             bind_phi_test(module.SFDQN_PHI)
+    elif name in ("sfdqn_phi", "tsfdqn_phi"):
+        cls = getattr(module, "SFDQN" if name == "sfdqn_phi" else "TSFDQN", None)
+        if cls is not None and hasattr(cls, "pre_train"):
+            cls.pre_train = lib_pre_train
     elif name == "agents.tsfdqn_phi":
         cls = getattr(module, "TSFDQN_PHI", None)
         if cls is None:  # not the reference's module: nothing to bind

@@ -696,6 +696,52 @@ int sfx_shard_tsf_update(sfx_t h, int policy, const float* S_dev, const int64_t*
 int sfx_shard_tsf_shared(sfx_t h, int policy, float* buf_dev, int unpack);
 int sfx_shard_tsf_select(sfx_t h, const float* s_dev, int task, int use_gpi, long long* key_dev);
 
+/* ---------------------------------------------------------------------------------------
+ * Pre-training of the reward features φ (kernels and the math: csrc/sfx_pre.h).  The
+ * single-file learned-φ agents open every run with pre_train(train_tasks, 5_000) (sfdqn_phi.py:800-873,
+ * :987; tsfdqn_phi.py:1036-1109, :1230), before any task is added to the agent: hence a handle of its
+ * own.  It holds the φ net of PhiFunction (sfdqn_phi.py:90-123; tsfdqn_phi.py:89 is the same net) --
+ * Linear(2 n_s + 1, hidden[0]) + ReLU, ..., Linear(hidden[n_hidden - 1], d) -- with the one Adam that
+ * lives for the whole phase (:106), and T reward rows w_t, each the Linear(d, 1, bias=False) `fit_w` of
+ * a task with an Adam of its own (:818-825).
+ * Limits (SFX_E_ARG, the message names the limit): 2 n_s + 1 <= 64, 1 to 4 hidden layers of width 1 to
+ * 256, 1 <= d <= 64, 1 <= max_batch <= 64, T >= 1.  The handle lives on the device that is current at
+ * sfx_pre_create and launches on `stream` (NULL = legacy default stream).
+ * ------------------------------------------------------------------------------------- */
+typedef struct sfx_pre_handle* sfx_pre_t;
+int sfx_pre_create(sfx_pre_t* out, int n_s, int d, int T, const int* hidden_host, int n_hidden, int max_batch);
+int sfx_pre_destroy(sfx_pre_t p);
+int sfx_pre_set_stream(sfx_pre_t p, void* stream);
+/* Packed parameter count of the φ net in torch packing. */
+int sfx_pre_numel(sfx_pre_t p);
+/* torch.optim.Adam of the φ net (sfdqn_phi.py:106: lr 1e-3) and of every fit_w (:822: lr 1e-3); the
+ * defaults are the reference's: 1e-3, 0, 1e-3, 0, 0.9, 0.999, 1e-8. */
+int sfx_pre_set_adam(sfx_pre_t p, double lr_phi, double wd_phi, double lr_w, double wd_w, double beta1,
+                     double beta2, double eps);
+/* The φ net (replaces building / reading PhiFunction._model, sfdqn_phi.py:97-105): torch parameters()
+ * packing, W [out][in] then b [out] per Linear. */
+int sfx_pre_load(sfx_pre_t p, const float* params_host);
+int sfx_pre_get(sfx_pre_t p, float* params_host);
+/* The φ net's Adam state (PhiFunction.optimiser, :106): m, v in the same packing, step = its step count. */
+int sfx_pre_load_adam(sfx_pre_t p, const float* m_host, const float* v_host, int step);
+int sfx_pre_get_adam(sfx_pre_t p, float* m_host, float* v_host, int* step);
+/* Row t (fit_ws[t] and fit_ws_optim[t], :818-825): w [d], its moments [d] and its own step count. */
+int sfx_pre_load_w(sfx_pre_t p, int t, const float* w_host, const float* m_host, const float* v_host, int step);
+int sfx_pre_get_w(sfx_pre_t p, int t, float* w_host, float* m_host, float* v_host, int* step);
+/* One minibatch update of task `task` (sfdqn_phi.py:856-865): loss = mse_loss(r, fit_w(φ(S, a, S1))),
+ * backward, then phi_learn_model.optimiser.step() and fit_w_optim.step() -- both on the gradients of the
+ * parameters as they were before the call.  The net's step count and row `task`'s advance by one, on the
+ * device; every other row, its moments and its count stay bit-identical.  S_dev / S1_dev [B][n_s],
+ * a_dev [B], r_dev [B], 1 <= B <= max_batch; loss_dev: a device scalar (no host read: the reference's
+ * loss.item() per step, :867, is what the caller avoids). */
+int sfx_pre_update(sfx_pre_t p, int task, const float* S_dev, const int64_t* a_dev, const float* r_dev,
+                   const float* S1_dev, int B, float* loss_dev);
+/* PhiFunction.forward (sfdqn_phi.py:109-120; the frozen net's callers :503, :773, tsfdqn_phi.py:945):
+ * phi_dev [B][d] from the current parameters, 1 <= B <= max_batch.  Row b of a B-row call equals the
+ * one-row call on that row bit for bit. */
+int sfx_pre_features(sfx_pre_t p, const float* S_dev, const int64_t* a_dev, const float* S1_dev, int B,
+                     float* phi_dev);
+
 #ifdef __cplusplus
 }
 #endif
