@@ -15,7 +15,8 @@
 //   k_pre_step  one workgroup per 16-row tile of every W_l (its 4 waves take 64 columns each; the last one
 //               sums the bias gradient) plus one for w_t: dW from the kept dZ_l and A_l, then Adam on the
 //               tile's own rows.  It reads no weight but the ones it steps.
-// The forward alone (TRAIN = false) is sfx_pre_features.
+// The forward alone (TRAIN = false) is sfx_pre_features; k_pre_rows is the same forward, one workgroup per 16-row
+// tile with the activations in LDS and no scratch of the handle (sfx_pre_features_rows, the runner's featurizer).
 //
 // Products run on v_mfma_f32_16x16x4_f32 with the operand layout of sfx_phiw.h: lane l supplies A[l & 15][l >> 4]
 // and B[l >> 4][l & 15] and holds D[4 (l >> 4) + r][l & 15].  A wave owns whole output tiles and walks the
@@ -90,10 +91,11 @@ __device__ __forceinline__ void pre_fold(floatx4 (&acc)[MT], float (*red)[MT * 4
   __syncthreads();  // red is free for the next layer
 }
 
-// Y[b][o] = act(Σ_k X[b][k] W[o][k] + bias[o]) for o < N; columns N .. ycols - 1 (the row pad) are written as zero
+// Y[b][o] = act(Σ_k X[b][k] W[o][k] + bias[o]) for o < N; columns N .. ycols - 1 (the row pad) are written as zero.
+// xs / ys: the row strides of X and Y in floats (multiples of 4); X and Y may live in global memory or in LDS.
 template <int MT>
-__device__ __forceinline__ void pre_fwd_layer(const float* W, const float* bias, const float* X, float* Y, int ys,
-                                              int ycols, int Kp, int N, int B, bool relu, int wave, int lane,
+__device__ __forceinline__ void pre_fwd_layer(const float* W, const float* bias, const float* X, int xs, float* Y,
+                                              int ys, int ycols, int Kp, int N, int B, bool relu, int wave, int lane,
                                               float (*red)[MT * 4][64]) {
   constexpr int CH = MT <= 2 ? 4 : 2;  // chunks of 16 k per trip: every load of a trip issued before its first use
   const int g = lane >> 4, c = lane & 15;
@@ -118,7 +120,7 @@ __device__ __forceinline__ void pre_fwd_layer(const float* W, const float* bias,
 #pragma unroll
         for (int t = 0; t < MT; ++t) {
           const int b = 16 * t + c;
-          x[u][t] = (b < B && k < kend) ? pre_ld4(X + (long long)b * Kp + k) : z4;
+          x[u][t] = (b < B && k < kend) ? pre_ld4(X + (long long)b * xs + k) : z4;
         }
       }
 #pragma unroll
@@ -239,8 +241,8 @@ __global__ __launch_bounds__(64 * PRE_WAVES) void k_pre_fwd(PreArgs A) {
     const bool last = l == NL - 1;
     float* Y = last ? (TRAIN ? A.phi : A.out) : A.act + G.offA[l + 1];
     const int ys = last ? d : G.Kp[l + 1];
-    pre_fwd_layer<MT>(A.p + G.offW[l], A.p + G.offB[l], A.act + G.offA[l], Y, ys, ys, G.Kp[l], G.N[l], B, !last, wave,
-                      lane, red);
+    pre_fwd_layer<MT>(A.p + G.offW[l], A.p + G.offB[l], A.act + G.offA[l], G.Kp[l], Y, ys, ys, G.Kp[l], G.N[l], B, !last,
+                      wave, lane, red);
     __syncthreads();
   }
   if constexpr (TRAIN) {
@@ -274,6 +276,60 @@ __global__ __launch_bounds__(64 * PRE_WAVES) void k_pre_fwd(PreArgs A) {
       __syncthreads();
     }
   }
+}
+
+// The forward alone on M rows, one workgroup per 16-row tile, every activation of the tile in LDS (two buffers,
+// ping-pong between layers): it reads the net's parameters and the rows' (s, a, s1) and writes φ, nothing else --
+// no handle scratch, so it may run on any stream, also inside another handle's captured graph, and M is not
+// bounded by max_batch.  Each layer is pre_fwd_layer<1> itself (same MFMA, operand layout, pre_slices split and
+// fold order), so row b of an M-row call equals sfx_pre_features of that row at B = 1 bit for bit.
+//
+// LDS row stride: lane (c = l & 15, g = l >> 4) reads row c at k + 4 g as one ds_read_b128, whose 16-lane groups
+// hold 8 rows at one g and 8 at g + 1 (banks: dword address mod 64, 4 per lane).  A stride of Kp = 64 / 128 / 256
+// floats puts the 8 rows of one g on the same 4 banks (8-way); stride / 4 ≡ 2 (mod 4) spreads one g over the even
+// 16-byte slots and the other over the odd ones: conflict-free.  PRE_LS = 264 is that for every Kp <= 256.
+constexpr int PRE_LS = 264;
+constexpr int PRE_ROWS_MAX = 65536;  // sfx_pre_features_rows' M limit (4096 workgroups)
+
+struct PreRowsArgs {
+  PreGeo G;
+  const float* p;
+  const float *S, *S1;
+  const int64_t* a;
+  float* phi;         // [M][d]
+  int M;
+  const int* cancel;  // runner steps: the gate's cancel word (a cancelled step writes nothing); null otherwise
+};
+
+__global__ __launch_bounds__(64 * PRE_WAVES) void k_pre_rows(PreRowsArgs A) {
+  __shared__ __attribute__((aligned(16))) float xa[2][16 * PRE_LS];
+  __shared__ float red[PRE_SLOTS][4][64];
+  if (A.cancel && step_cancelled(A.cancel)) return;  // uniform over the grid
+  const PreGeo& G = A.G;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, NL = G.NL, d = G.d;
+  const long long row0 = 16LL * blockIdx.x;
+  const int B = (int)min(16LL, (long long)A.M - row0);
+  {
+    const int Kp0 = G.Kp[0], n_s = G.n_s;
+    for (int j = tid; j < B * Kp0; j += 64 * PRE_WAVES) {
+      const int b = j / Kp0, k = j - b * Kp0;
+      float v = 0.f;
+      if (k < n_s) v = A.S[(row0 + b) * n_s + k];
+      else if (k == n_s) v = (float)A.a[row0 + b];
+      else if (k < G.n_in) v = A.S1[(row0 + b) * n_s + (k - n_s - 1)];
+      xa[0][b * PRE_LS + k] = v;
+    }
+  }
+  __syncthreads();
+  // hidden layers LDS -> LDS, the output layer LDS -> global: two call sites, so every access keeps its address space
+  for (int l = 0; l < NL - 1; ++l) {
+    pre_fwd_layer<1>(A.p + G.offW[l], A.p + G.offB[l], xa[l & 1], PRE_LS, xa[(l + 1) & 1], PRE_LS, G.Kp[l + 1], G.Kp[l],
+                     G.N[l], B, true, wave, lane, red);
+    __syncthreads();
+  }
+  const int l = NL - 1;
+  pre_fwd_layer<1>(A.p + G.offW[l], A.p + G.offB[l], xa[l & 1], PRE_LS, A.phi + row0 * d, d, d, G.Kp[l], G.N[l], B, false,
+                   wave, lane, red);
 }
 
 template <int MT>

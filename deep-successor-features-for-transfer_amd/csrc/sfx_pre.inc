@@ -228,4 +228,28 @@ int sfx_pre_features(sfx_pre_t h, const float* S, const int64_t* a, const float*
   return SFX_OK;
 }
 
+namespace {
+
+// k_pre_rows on `stream` (the runner: the ψ handle's, inside its captured step graph).  No allocation, no
+// scratch of the handle; cancel: a runner gate's cancel word or null.
+int pre_rows_body(sfx_pre_handle* h, hipStream_t stream, const float* S, const int64_t* a, const float* S1, int M,
+                  float* phi, const int* cancel) {
+  PreRowsArgs A{};
+  A.G = h->G;
+  A.p = h->p, A.S = S, A.S1 = S1, A.a = a, A.phi = phi, A.M = M, A.cancel = cancel;
+  k_pre_rows<<<cdiv(M, 16), 64 * PRE_WAVES, 0, stream>>>(A);
+  LAUNCHCHK();
+  return SFX_OK;
+}
+void pre_dims(const sfx_pre_handle* h, int* n_s, int* d) { *n_s = h->G.n_s, *d = h->G.d; }
+
+}  // namespace
+
+int sfx_pre_features_rows(sfx_pre_t h, const float* S, const int64_t* a, const float* S1, int M, float* phi) {
+  if (!h) SFX_FAIL(SFX_E_ARG, "sfx_pre_features_rows: null handle");
+  if (!S || !a || !S1 || !phi) SFX_FAIL(SFX_E_ARG, "sfx_pre_features_rows: null argument");
+  if (M < 1 || M > PRE_ROWS_MAX) SFX_FAIL(SFX_E_ARG, "sfx_pre_features_rows: limit 1 <= M <= 65536");
+  return pre_rows_body(h, h->stream, S, a, S1, M, phi, nullptr);
+}
+
 #undef PRE_BY_TILES

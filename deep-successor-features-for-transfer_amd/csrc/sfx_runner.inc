@@ -16,6 +16,9 @@
 //          TSFDQN_PHI.update_deep_models (φ̃ = φ ⊙ t, g_i and h plain Linears).
 //          Both step the φ net, w_i, its bias, λ_i (and g_i, h) in place, so every one of their kernels
 //          honours the gate's cancel word; no look-ahead and no device replay yet.
+// sfx_runner_featurizer (active and tsf): a frozen pre-trained φ net (sfx_pre_t); each step with an update
+// recomputes its minibatch's φ rows from (s, a, s1) with k_pre_rows between the gate and the update -- the
+// main phase of sfdqn_phi.py / tsfdqn_phi.py.  The staged φ rows and the env's φ are then never read.
 // The env and the replay ring stay on the host (north_star); the device work of a step is one
 // hipGraph: k_gate -> the step's update -> the action for the next state -> publish.
 //
@@ -76,8 +79,19 @@ RunnerLayout runner_layout(int B, int n_s, int d) {
 
 }  // namespace
 
+struct sfx_pre_handle;  // sfx_pre.inc
+namespace {
+int pre_rows_body(sfx_pre_handle* p, hipStream_t stream, const float* S, const int64_t* a, const float* S1, int M,
+                  float* phi, const int* cancel);
+void pre_dims(const sfx_pre_handle* p, int* n_s, int* d);
+const char* const RUN_NAMES[] = {"all", "active", "tsf", "sharded", "sharded_tsf", "phi", "tsf_phi"};
+}  // namespace
+
 struct sfx_runner {
   sfx_handle* h = nullptr;
+  // sfx_runner_featurizer: the frozen φ net whose forward of the staged minibatch replaces the staged φ rows
+  // (active and TSF schedules); caller-owned
+  sfx_pre_handle* feat = nullptr;
   int B = 32, cap = 0, ep_len = 500, sel_use_gpi = 1, pipeline = 1;
   int schedule = RUN_ALL, upd_use_gpi = 1;  // sfx_runner_config
   float gamma = 0.9f, eps = 0.1f, alpha_w = 1e-3f, p_end = 0.f;
@@ -482,6 +496,10 @@ int runner_body(sfx_runner* R, bool have, bool lms, sfx_runner::StepFlags fl = {
                          at(R->lay.gamma), R->B, R->upd_use_gpi, R->phi_bias + R->task, R->phi_lam + R->task, R->dloss,
                          nullptr));
     } else if (have) {  // pre: the previous step's select forwarded this minibatch (select_ahead_body)
+      // frozen featurizer: the minibatch's φ rows from its (s, a, s1), over the staged ones the gate copied
+      if (R->feat)
+        RC(pre_rows_body(R->feat, h->stream, at(R->lay.s), a, at(R->lay.s1), R->B,
+                         reinterpret_cast<float*>(R->dst + R->lay.phi), h->dcancel));
       if (R->schedule == RUN_TSF)
         RC(tsf_body(h, R->task, at(R->lay.s), a, at(R->lay.rb), at(R->lay.phi), at(R->lay.s1), at(R->lay.gamma), R->B,
                     R->upd_use_gpi, R->dloss, nullptr, nullptr, pre));
@@ -544,7 +562,7 @@ int runner_launch(sfx_runner* R, bool have, bool lms, int nsteps = 1, bool launc
                    h->spec_rounds * RUN_SCHEDULES + R->schedule,
                    R->dev_replay + 2 * R->upd_use_gpi + 4 * nsteps + 128 * fl0.pre + 256 * fl0.ahead + 512 * fl0.par},
                h->mask, {R->dst, R->hst, R->go, R->res, phi_sched(R->schedule) ? R->phi_bias : nullptr,
-                         phi_sched(R->schedule) ? R->phi_lam : nullptr});
+                         phi_sched(R->schedule) ? R->phi_lam : nullptr, R->feat});
   return run_graph(h, key, [&]() -> int {
     const unsigned long long m0 = h->mask;
     int rc = SFX_OK;
@@ -1242,6 +1260,10 @@ int sfx_runner_layout(sfx_runner_t R, int64_t* offsets_host) {
 
 int sfx_runner_config(sfx_runner_t R, int schedule, int use_gpi, float p_end) {
   if (!R || schedule < RUN_ALL || schedule > RUN_TSF_PHI || p_end < 0.f || p_end > 1.f) SFX_FAIL(SFX_E_ARG, "bad args");
+  if (R->feat && schedule != RUN_ACTIVE && schedule != RUN_TSF)
+    SFX_FAIL(SFX_E_STATE, std::string("sfx_runner_config: a featurizer is set (sfx_runner_featurizer), which runs with the "
+                                      "active and tsf schedules only, not with schedule ") +
+                              std::to_string(schedule) + " (" + RUN_NAMES[schedule] + "); clear it first");
   if ((schedule == RUN_TSF || schedule == RUN_SHARD_TSF) && !R->h->tsf)
     SFX_FAIL(SFX_E_STATE, "sfx_runner_config: tsf schedule needs sfx_tsf_setup");
   if ((schedule == RUN_SHARD || schedule == RUN_SHARD_TSF) && R->h->comm_world < 1)
@@ -1277,6 +1299,9 @@ int sfx_runner_device_replay(sfx_runner_t R, int enable) {
   if (R->pre_n) SFX_FAIL(SFX_E_STATE, "sfx_runner_device_replay: a step is pre-launched");
   if (enable && phi_sched(R->schedule))
     SFX_FAIL(SFX_E_STATE, "sfx_runner_device_replay: the learned-φ schedules (phi, tsf_phi) keep the replay on the host");
+  if (enable && R->feat)
+    SFX_FAIL(SFX_E_STATE, "sfx_runner_device_replay: a featurizer is set (sfx_runner_featurizer), which keeps the replay "
+                          "on the host; clear it first");
   if (enable && !R->drs) {
     if (R->lay.ax - R->lay.snext > (size_t)REPLAY_TAIL_MAX)
       SFX_FAIL(SFX_E_ARG, "sfx_runner_device_replay: state / feature sizes exceed the gate's staging");
@@ -1289,6 +1314,32 @@ int sfx_runner_device_replay(sfx_runner_t R, int enable) {
   }
   R->dev_replay = enable ? 1 : 0;
   R->dring_dirty = true;
+  return SFX_OK;
+}
+
+int sfx_runner_featurizer(sfx_runner_t R, sfx_pre_t p) {
+  if (!R) SFX_FAIL(SFX_E_ARG, "sfx_runner_featurizer: null runner");
+  RunnerScope scope(R->h);
+  RC(runner_complete(R));
+  if (R->pre_n) SFX_FAIL(SFX_E_STATE, "sfx_runner_featurizer: a step is pre-launched");
+  if (p) {
+    int n_s = 0, d = 0;
+    pre_dims(p, &n_s, &d);
+    if (n_s != R->h->n_s || d != R->h->d)
+      SFX_FAIL(SFX_E_ARG, "sfx_runner_featurizer: the featurizer's n_s = " + std::to_string(n_s) + ", d = " +
+                              std::to_string(d) + " differ from the handle's n_s = " + std::to_string(R->h->n_s) +
+                              ", d = " + std::to_string(R->h->d));
+    if (R->schedule != RUN_ACTIVE && R->schedule != RUN_TSF)
+      SFX_FAIL(SFX_E_STATE, std::string("sfx_runner_featurizer: a featurizer runs with the active and tsf schedules only, "
+                                        "not with schedule ") +
+                                std::to_string(R->schedule) + " (" + RUN_NAMES[R->schedule] + ")");
+    if (R->dev_replay)
+      SFX_FAIL(SFX_E_STATE, "sfx_runner_featurizer: a featurizer keeps the replay on the host (device replay is on; "
+                            "switch it off first)");
+    clear_graphs(R->h);  // the step graphs hold the net's geometry and pointers: none may outlive a handle's address
+  }
+  if (p != R->feat) R->chain = false;
+  R->feat = p;
   return SFX_OK;
 }
 
@@ -1326,6 +1377,9 @@ int runner_run(sfx_runner* R, int n);
 // next minibatch; TSF: with its kernels on the step stream) (SFX_AHEAD=0: off)
 bool runner_ahead_ok(const sfx_runner* R) {
   if (!R->ahead_on || R->dev_replay || phi_sched(R->schedule)) return false;  // learned φ: no look-ahead yet
+  // frozen featurizer: the active schedule's look-ahead block holds states only and stays; the TSF one carries
+  // the next minibatch's φ rows from the host, which are not the net's
+  if (R->feat && R->schedule != RUN_ACTIVE) return false;
   if (R->schedule == RUN_ALL) return can_fuse_ahead(R->h, R->B + 1, R->B);
   // the sharded all-task step whose maxima come from k_qmax launches (the fused maxima accumulate
   // round 0's GPI terms in the step's own S1 forward)

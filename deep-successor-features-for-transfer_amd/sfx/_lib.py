@@ -156,6 +156,8 @@ SIGNATURES = {
     "sfx_pre_get_w": (_I, [_VP, _I, _FP, _FP, _FP, _IP]),
     "sfx_pre_update": (_I, [_VP, _I, _VP, _VP, _VP, _VP, _I, _VP]),
     "sfx_pre_features": (_I, [_VP, _VP, _VP, _VP, _I, _VP]),
+    "sfx_pre_features_rows": (_I, [_VP, _VP, _VP, _VP, _I, _VP]),
+    "sfx_runner_featurizer": (_I, [_VP, _VP]),
 }
 
 # env callbacks of sfx_runner_create (include/sfx.h)

@@ -12,10 +12,14 @@ unchanged on libsfx:
   library classes become sfx's and the TSF agents' ``update_successor`` one libsfx call;
   ``agents.sfdqn_phi`` and ``agents.tsfdqn_phi`` load as they are too, the latter's
   ``TSFDQN_PHI.update_deep_models`` becoming one libsfx call (sfx_tsf_phi_update);
-* the single-file learned-φ agents ``sfdqn_phi`` and ``tsfdqn_phi`` load as they are; their opening phase
-  ``SFDQN.pre_train`` / ``TSFDQN.pre_train`` becomes ``sfx.pretrain.pre_train`` (one libsfx call per
-  minibatch update, sfx_pre_update) and ``self.learnt_phi`` an ``sfx.pretrain.LearntPhi``; everything else in
-  those modules stays the user's;
+* the single-file learned-φ agents ``sfdqn_phi`` and ``tsfdqn_phi`` load as they are and are bound whole: their
+  opening phase ``SFDQN.pre_train`` / ``TSFDQN.pre_train`` becomes ``sfx.pretrain.pre_train`` (one libsfx call per
+  minibatch update, sfx_pre_update) and ``self.learnt_phi`` an ``sfx.pretrain.LearntPhi`` (the frozen net on the
+  device, one launch per call); in the main phase ``sfdqn_phi.DeepSF`` / ``tsfdqn_phi.DeepTSF`` are sfx's classes
+  (no ``task.get_w()``, no ``true_w``) and ``tsfdqn_phi.TSFDQN``'s update_successor / get_test_action /
+  update_test_reward_mapper libsfx calls (the mapper's φ from ``self.phi`` once ``learnt_phi`` is set, its
+  diagnostic draw only under the module's ``print_debug``); the agents' loops, ``test_agent`` and
+  ``sfdqn_phi.SFDQN``'s own test mapper stay the user's;
 * ``agents.buffer`` is sfx's ``ReplayBuffer`` (the reference's API over a device-resident ring,
   the same ``np.random`` index draws; ``sfx/dropin/agents/buffer.py``);
 * every other ``agents`` module, ``utils``, ``tasks`` and the scripts themselves are the user's, untouched.

@@ -16,10 +16,22 @@ and loss coefficient (DeepSF_TSF_PHI.tsf_phi_test_action / tsf_phi_test_update);
 ``agents.sfdqn_phi``'s update_test_reward_mapper (:263-305) likewise (DeepSF_PHI.phi_test_update).
 Where the agent's modules are not the shapes the library runs, those methods fall back to the
 agent's own torch code, after the device's φ net, g_i and h are copied back into its modules -- as
-``test_agent`` is wrapped to do once per test episode.  The single-file learned-φ agents ``sfdqn_phi`` /
-``tsfdqn_phi`` keep everything but their opening phase: ``SFDQN.pre_train`` (sfdqn_phi.py:800-873) /
-``TSFDQN.pre_train`` (tsfdqn_phi.py:1036-1109) becomes ``sfx.pretrain.pre_train``.  Nothing else of the user's
-agents is touched.
+``test_agent`` is wrapped to do once per test episode.
+
+The single-file learned-φ agents ``sfdqn_phi`` / ``tsfdqn_phi`` are bound whole.  Their opening phase
+``SFDQN.pre_train`` (sfdqn_phi.py:800-873) / ``TSFDQN.pre_train`` (tsfdqn_phi.py:1036-1109) becomes
+``sfx.pretrain.pre_train``, which leaves ``self.learnt_phi`` a frozen net on the device (sfx.pretrain.LearntPhi).
+Their main phase is the other single-file agents' but for where φ comes from -- ``self.phi = self.learnt_phi``
+(sfdqn_phi.py:482-485), ``phi = self.phi(s_enc, a, s1_enc)`` (:503) -- so ``sfdqn_phi.DeepSF`` /
+``tsfdqn_phi.DeepTSF`` become subclasses of the single-file library classes that never call ``task.get_w()`` and
+keep no ``true_w`` (tasks/hopper_phi.py's get_w raises; the reference's classes dropped both), and
+``tsfdqn_phi.TSFDQN``'s update_successor / get_test_action / update_test_reward_mapper are bound as
+``tsfdqn.TSFDQN``'s are, with the reference's two differences: the mapper's φ is ``self.phi(s, a, s1)`` when
+``self.learnt_phi`` is set, and its diagnostic block -- with the ``random.randint(1, 1000)`` draw -- runs only when
+the module's ``print_debug`` is true.  The stored φ reaches update_successor as data (``phis.detach()``,
+sfdqn_phi.py:369-371), which is how sfx_update / sfx_tsf_update take it.  The agents' ``test_agent`` loops (10
+episodes per test task), ``sfdqn_phi.SFDQN``'s own test mapper and everything else stay the user's; sfx.lockstep
+does not cover these two agents.
 """
 from __future__ import annotations
 
@@ -46,6 +58,25 @@ class SingleFileDeepTSF(_tsf.DeepTSF):
     def __init__(self, pytorch_model_handle, use_true_reward, target_update_ev=1000, **kwargs):
         super().__init__(pytorch_model_handle, target_update_ev=target_update_ev, use_true_reward=use_true_reward,
                          **kwargs)
+
+
+class _NoTrueW:
+    """sfdqn_phi.py:161, :224, :232 / tsfdqn_phi.py likewise: no ``true_w`` list, no ``task.get_w()`` call."""
+
+    def reset(self):
+        super().reset()
+        del self.true_w
+
+    def _note_true_w(self, task):
+        pass
+
+
+class SingleFileDeepSFPhi(_NoTrueW, SingleFileDeepSF):
+    """sfdqn_phi.py's DeepSF: sfdqn.py's without the true reward weights; φ arrives in the transitions as data."""
+
+
+class SingleFileDeepTSFPhi(_NoTrueW, SingleFileDeepTSF):
+    """tsfdqn_phi.py's DeepTSF: tsfdqn.py's without the true reward weights."""
 
 
 def tsf_update_successor(self, transitions, policy_index, use_gpi=True):
@@ -107,6 +138,37 @@ def tsf_update_test_reward_mapper(self, w_approx, omegas, optim, task, r, s, a, 
     return loss, l2, l1
 
 
+def _print_debug(agent) -> bool:
+    """The ``print_debug`` global of the agent's own module (tsfdqn_phi.py:1160, set by its __main__ block)."""
+    import sys
+
+    return bool(getattr(sys.modules.get(type(agent).__module__), "print_debug", False))
+
+
+def tsf_phi_update_test_reward_mapper(self, w_approx, omegas, optim, task, r, s, a, s1, a1):
+    """tsfdqn_phi.py's TSFDQN.update_test_reward_mapper: tsf_update_test_reward_mapper with the reference's two
+    differences -- φ is ``self.phi(s, a, s1)`` when ``self.learnt_phi`` is set (the frozen net, one library call),
+    else ``task.features``; the diagnostic block and its ``random.randint(1, 1000)`` draw sit under the module's
+    ``print_debug``, so Python's random stream is the reference's.  Returns (loss, l2, l1)."""
+    if self.h_function is None:
+        raise Exception('Affine Function (h) is not initialized')
+    with torch.no_grad():
+        phi = task.features(s, a, s1) if self.learnt_phi is None else self.phi(s, a, s1)
+    gw, go = optim.param_groups[0], optim.param_groups[1]
+    for grp in (gw, go):
+        if tuple(grp.get("betas", (0.9, 0.999))) != (0.9, 0.999) or grp.get("eps", 1e-8) != 1e-8:
+            raise NotImplementedError("sfx: the test reward mapper's Adam runs with betas (0.9, 0.999), eps 1e-8")
+    hp = self.hyperparameters
+    loss, l2, l1 = self.sf.tsf_test_update(w_approx, omegas, phi, r, s, a, s1, a1, gamma=self.gamma,
+                                           beta=hp['beta_loss_coefficient'], lasso=hp['omegas_l1_coefficient'],
+                                           lr_w=gw['lr'], wd_w=gw['weight_decay'], lr_o=go['lr'],
+                                           wd_o=go['weight_decay'])
+    if _print_debug(self):
+        if self.total_training_steps % 1000 == 0 and random.randint(1, 1000) < 10:
+            print(f'Target Task {task} omegas {omegas.detach()} weights {w_approx.weight.detach()}')
+    return loss, l2, l1
+
+
 def _synced(method):
     """Run the agent's own method after the device's g_i / h are copied into its modules (the test
     tasks' reward mapper, tsfdqn.py:874-997, reads them in torch)."""
@@ -121,11 +183,11 @@ def _synced(method):
     return run
 
 
-def patch_tsf_agent(cls) -> None:
+def patch_tsf_agent(cls, mapper=tsf_update_test_reward_mapper) -> None:
     cls.update_successor = tsf_update_successor
     if hasattr(cls, "get_test_action") and hasattr(cls, "update_test_reward_mapper"):
         cls.get_test_action = tsf_get_test_action
-        cls.update_test_reward_mapper = tsf_update_test_reward_mapper
+        cls.update_test_reward_mapper = mapper
     for name in ("test_agent",):
         m = getattr(cls, name, None)
         if m is not None and not getattr(m, "__sfx_bound__", False):
@@ -265,6 +327,12 @@ def patch(name: str, module) -> None:
         cls = getattr(module, "SFDQN" if name == "sfdqn_phi" else "TSFDQN", None)
         if cls is not None and hasattr(cls, "pre_train"):
             cls.pre_train = lib_pre_train
+        if name == "sfdqn_phi":
+            module.DeepSF = SingleFileDeepSFPhi
+        else:
+            module.DeepTSF = SingleFileDeepTSFPhi
+            if cls is not None:
+                patch_tsf_agent(cls, tsf_phi_update_test_reward_mapper)
     elif name == "agents.tsfdqn_phi":
         cls = getattr(module, "TSFDQN_PHI", None)
         if cls is None:  # not the reference's module: nothing to bind

@@ -53,11 +53,16 @@ class DeepSF(_deep.DeepSF):
         g1 = optim.param_groups[1] if len(optim.param_groups) > 1 else g0
         return (g0["lr"], g0.get("weight_decay", 0.0)), (g1["lr"], g1.get("weight_decay", 0.0))
 
+    def _note_true_w(self, task):
+        """The task's true reward weights, kept for the agents' w-error statistic (sfdqn.py:194, :203); the
+        learned-φ single-file classes keep none (their tasks' get_w raises)."""
+        self.true_w.append(task.get_w())
+
     def add_training_task(self, task, source=None):
         """features/deep_sequential.py:40-73 (w first, then the ψ networks)."""
         self._flush()
         self._sync_host()
-        true_w = task.get_w()
+        self._note_true_w(task)
         n_features = task.feature_dim()
         fit_w = torch.Tensor(1, n_features).uniform_(-0.01, 0.01).to(self.device)
         # built on the CPU and moved: its (overwritten) init draw comes from the CPU generator, as
@@ -65,7 +70,6 @@ class DeepSF(_deep.DeepSF):
         w_approx = torch.nn.Linear(n_features, 1, bias=False).to(self.device)
         with torch.no_grad():
             w_approx.weight = torch.nn.Parameter(fit_w)
-        self.true_w.append(true_w)
         list.append(self.fit_w, w_approx)
         self._psi.append(self.build_successor(task, source, w_approx))
         self.n_tasks = len(self._psi)

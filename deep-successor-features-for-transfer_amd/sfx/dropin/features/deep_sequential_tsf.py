@@ -113,14 +113,13 @@ class DeepTSF(_seq.DeepSF):
         self._sync_host()
         if self._eng is not None:
             raise NotImplementedError("sfx DeepTSF: add every training task before the first update")
-        true_w = task.get_w()
+        self._note_true_w(task)
         n_features = task.feature_dim()
         fit_w = torch.Tensor(1, n_features).uniform_(-0.01, 0.01).to(self.device)
         # built on the CPU and moved (see features.deep_sequential.add_training_task)
         w_approx = torch.nn.Linear(n_features, 1, bias=False).to(self.device)
         with torch.no_grad():
             w_approx.weight = torch.nn.Parameter(fit_w)
-        self.true_w.append(true_w)
         list.append(self.fit_w, w_approx)
         self._psi.append(self.build_successor(task, source, w_approx, g_function_model, h_function_model))
         self.n_tasks = len(self._psi)

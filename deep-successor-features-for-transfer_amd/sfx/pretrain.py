@@ -69,6 +69,8 @@ def pack_module(module: torch.nn.Module) -> torch.Tensor:
 class PreEngine:
     """The φ net, its Adam, and T reward rows with theirs, on one GPU (include/sfx.h sfx_pre_*)."""
 
+    ROWS_MAX = 65536     # sfx_pre_features_rows' limit on the rows of one launch
+
     def __init__(self, n_s: int, d: int, T: int, hidden: Sequence[int] = (128, 256), max_batch: int = 32,
                  device=None):
         if not torch.cuda.is_available():
@@ -165,7 +167,8 @@ class PreEngine:
         return out
 
     def features(self, S, a, S1) -> torch.Tensor:
-        """φ [B, d] of the current net; more rows than max_batch go in chunks (rows are independent)."""
+        """φ [B, d] of the current net: one sfx_pre_features_rows launch whatever max_batch is (up to ROWS_MAX rows
+        a launch); row b equals the one-row call bit for bit."""
         S, S1 = self._dev(S, torch.float32).reshape(-1, self.n_s), self._dev(S1, torch.float32).reshape(-1, self.n_s)
         a = self._dev(a, torch.long).reshape(-1)
         B = S.shape[0]
@@ -173,10 +176,10 @@ class PreEngine:
             raise ValueError("S, a, S1 disagree on the number of rows")
         out = torch.empty(B, self.d, dtype=torch.float32, device=self.device)
         self._bind_stream()
-        for lo in range(0, B, self.max_batch):
-            n = min(self.max_batch, B - lo)
-            check(lib.sfx_pre_features(self._h, S[lo:].data_ptr(), a[lo:].data_ptr(), S1[lo:].data_ptr(), n,
-                                       out[lo:].data_ptr()), "sfx_pre_features")
+        for lo in range(0, B, self.ROWS_MAX):
+            n = min(self.ROWS_MAX, B - lo)
+            check(lib.sfx_pre_features_rows(self._h, S[lo:].data_ptr(), a[lo:].data_ptr(), S1[lo:].data_ptr(), n,
+                                            out[lo:].data_ptr()), "sfx_pre_features_rows")
         return out
 
 

@@ -241,7 +241,14 @@ class NativeEnvLoop:
     env: None for the built-in synthetic Reacher-shape task, or an object with
     ``reset(task) -> s0`` and ``step(task, a) -> (s1, phi, r, terminal)`` (numpy / floats),
     called through C callbacks (agents/agent.py's Task interface: tasks/task.py).  Under the learned-φ
-    schedules the env's φ is not used and ``step`` may return None for it.
+    schedules, and while a featurizer is set, the env's φ is not used and ``step`` may return None for it.
+
+    featurizer: a sfx.pretrain.PreEngine, a LearntPhi or None ("active" and "tsf" only, host replay only): the
+    frozen pre-trained φ net of the single-file learned-φ agents' main phase (sfdqn_phi.py:482-485, :503).  Every
+    step with an update then computes its minibatch's φ rows from (s, a, s1) on the device, bit for bit what the
+    net gives one row at a time; the env's and the replay's φ are never read.  "active" keeps its look-ahead,
+    "tsf" does not look ahead meanwhile.  The loop keeps the engine alive; its parameters may change between
+    runs, not during one.
     """
 
     FIELDS = ("s", "s1", "phi", "a", "gamma", "snext", "phi1", "r1", "rb")
@@ -251,17 +258,17 @@ class NativeEnvLoop:
     def __init__(self, engine: SFEngine, batch: int = 32, capacity: int = 1_000_000, gamma: float = 0.9,
                  epsilon: float = 0.1, alpha_w: float = 1e-3, episode_len: int = 500, use_gpi: bool = True,
                  seed: int = 1, env=None, schedule: str = "all", upd_use_gpi: bool = True, p_end: float = 0.0,
-                 device_replay: bool = False, phi_bias=None, phi_lambda=None):
+                 device_replay: bool = False, phi_bias=None, phi_lambda=None, featurizer=None):
         import ctypes as C
 
         from ._lib import ENV_RESET_FN, ENV_STEP_FN, check, lib
 
         self.eng, self.B, self._lib, self._check, self._C = engine, batch, lib, check, C
         self._cbs = None
+        self._featurizer = None
         reset_fn = step_fn = None
         if env is not None:
             n_s, d = engine.n_s, engine.d
-            phi_unused = schedule in self.PHI_SCHEDULES
 
             def _reset(_ctx, task, s0):
                 try:
@@ -275,7 +282,7 @@ class NativeEnvLoop:
                 try:
                     ns, ph, rr, tt = env.step(task, a)
                     np.ctypeslib.as_array(s1, shape=(n_s,))[:] = np.asarray(ns, np.float32).reshape(n_s)
-                    if ph is None and phi_unused:
+                    if ph is None and (self.schedule in self.PHI_SCHEDULES or self._featurizer is not None):
                         np.ctypeslib.as_array(phi, shape=(d,))[:] = 0.0
                     else:
                         np.ctypeslib.as_array(phi, shape=(d,))[:] = np.asarray(ph, np.float32).reshape(d)
@@ -302,8 +309,19 @@ class NativeEnvLoop:
             self.set_phi_scalars(phi_bias, phi_lambda)
         self.set_schedule(schedule, upd_use_gpi, p_end)
         self.task_index = 0
+        if featurizer is not None:
+            self.set_featurizer(featurizer)
         if device_replay:
             self.set_device_replay(True)
+
+    def set_featurizer(self, featurizer):
+        """sfx_runner_featurizer: a PreEngine, a LearntPhi or None (clears it); between runs."""
+        eng = getattr(featurizer, "engine", featurizer)
+        if eng is not None and getattr(eng, "handle", None) is None:
+            raise ValueError("featurizer: a sfx.pretrain.PreEngine, a LearntPhi over one, or None")
+        self._check(self._lib.sfx_runner_featurizer(self._r, eng.handle if eng is not None else None),
+                    "sfx_runner_featurizer")
+        self._featurizer = eng
 
     def set_device_replay(self, on: bool):
         """SURVEY §8f rank 2 (opt-in; the north_star keeps the replay on the host): the ring in

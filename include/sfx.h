@@ -376,14 +376,15 @@ int sfx_runner_layout(sfx_runner_t r, int64_t* offsets_host /* [10] */);
  * reports zero pre-steps).  use_gpi: next actions of the
  * update by GPI (1) or the own head (0).  p_end: episode-end probability per step of the
  * built-in synthetic task (γ = 0 on that transition; 0 = never, like tasks/reacher.py:112).
- * Call between runs (before sfx_runner_set_task). */
+ * With a featurizer set (sfx_runner_featurizer) only schedules 1 and 2 are accepted (SFX_E_STATE
+ * naming the schedule).  Call between runs (before sfx_runner_set_task). */
 int sfx_runner_config(sfx_runner_t r, int schedule, int use_gpi, float p_end);
 /* Device-resident replay (opt-in -- the north_star keeps the replay on the
  * host, and so does the headline bench): the ring moves to HBM, each step hands the device only
  * its transition, and the step's gate kernel appends it and draws the uniform minibatch (index
  * function replay_index in csrc/sfx_kernels.h).  The host ring stays as a mirror (prefill,
  * records); switching uploads it before the next run.  Replaces agents/buffer.py:34-64.
- * Refused with SFX_E_STATE under the learned-φ schedules (5, 6). */
+ * Refused with SFX_E_STATE under the learned-φ schedules (5, 6) and while a featurizer is set. */
 int sfx_runner_device_replay(sfx_runner_t r, int enable);
 /* The learned-φ schedules' per-task scalars: two caller-owned device arrays of T floats, element t
  * task t's reward-model bias (fit_w[t].bias) and loss coefficient λ_t (agents/sfdqn_phi.py:62-70).
@@ -432,7 +433,8 @@ int sfx_runner_retried(sfx_runner_t r, long long* retried);
  * the LMS fit).  pre_steps: steps that started so; own_forward_steps: steps with an update that ran
  * their own forward (their minibatch sampled the slot of their own transition, whose next state
  * was unknown a step early; the first step of a run; after a target sync or a drain).  The
- * learned-φ schedules (5, 6) do not look ahead: both counts stay zero. */
+ * learned-φ schedules (5, 6) do not look ahead: both counts stay zero; nor does schedule 2 while a
+ * featurizer is set (sfx_runner_featurizer), schedule 1 still does. */
 int sfx_runner_ahead_stats(sfx_runner_t r, long long* pre_steps, long long* own_forward_steps);
 /* Steps whose host rounds found later steps cancelled at their gates: those steps' launches ran
  * (committing nothing) over the transient buffers the rounds read, so the step's forward and
@@ -741,6 +743,33 @@ int sfx_pre_update(sfx_pre_t p, int task, const float* S_dev, const int64_t* a_d
  * one-row call on that row bit for bit. */
 int sfx_pre_features(sfx_pre_t p, const float* S_dev, const int64_t* a_dev, const float* S1_dev, int B,
                      float* phi_dev);
+/* The same forward on M rows, 1 <= M <= 65536 whatever max_batch is: one launch, one workgroup per 16-row
+ * tile, every activation in LDS (k_pre_rows, csrc/sfx_pre.h).  It reads the parameters and the inputs and
+ * writes phi_dev [M][d], no scratch of the handle.  Row b equals sfx_pre_features of that row at B = 1 bit
+ * for bit (so also row b of any B-row sfx_pre_features call), and two calls give the same bits.  A null
+ * argument or M out of range: SFX_E_ARG, the message names the limit.  Runs on the handle's stream. */
+int sfx_pre_features_rows(sfx_pre_t p, const float* S_dev, const int64_t* a_dev, const float* S1_dev, int M,
+                          float* phi_dev);
+
+/* A frozen featurizer for the runner's active-task (1) and TSF (2) schedules: the main phase of the
+ * single-file learned-φ agents (sfdqn_phi.py:482-485, :503; tsfdqn_phi.py likewise), where φ is no longer
+ * task.features on the host but the pre-trained net.  With p set, every step that has an update launches
+ * k_pre_rows on its staged minibatch (s, a, s1; B rows) on the ψ handle's stream, after the gate and before
+ * the update, as a node of its own in the step graph; it writes the φ rows the update reads.  The net is
+ * frozen during the phase and row b of the launch equals the one-row forward, so these rows are bit for
+ * bit what the reference stored at append time.  The host's staged φ rows and the env callback's φ output
+ * are never read (the callback may leave phi_host untouched).  A step cancelled at its gate writes nothing.
+ *   p = NULL clears it: the runner then behaves exactly as one that never had a featurizer.
+ *   p's n_s and d must equal the handle's (SFX_E_ARG naming both values).
+ *   Schedules 1 and 2 only, host replay only: whichever of sfx_runner_featurizer / sfx_runner_config /
+ *   sfx_runner_device_replay comes second refuses the combination with SFX_E_STATE, naming the schedule.
+ *   Look-ahead: schedule 1 keeps it (its look-ahead block holds states only; results are bit-identical with
+ *   it on or off); schedule 2 does not look ahead while a featurizer is set -- its block would carry the next
+ *   minibatch's φ rows from the host -- and sfx_runner_ahead_stats then reports zero pre-steps.
+ *   Lifetime: p must outlive the runner or be cleared first.  Its parameters may change between runs
+ *   (sfx_pre_update, sfx_pre_load) and must not change during sfx_runner_run.
+ * Call between runs. */
+int sfx_runner_featurizer(sfx_runner_t r, sfx_pre_t p);
 
 #ifdef __cplusplus
 }
