@@ -41,6 +41,7 @@
 #include "sfx_tsfphi.h"
 #include "sfx_phitest.h"
 #include "sfx_pre.h"
+#include "sfx_testphase.h"
 #include "../../include/sfx.h"
 
 using namespace sfx;

@@ -2550,24 +2550,28 @@ __global__ void k_lms(float* __restrict__ w, const float* __restrict__ phi, cons
 // N = 1), d_p = ∂w + wd·w, w += -lr·d_p (torch/optim/sgd.py single-tensor, no momentum).  The
 // loss is the pre-step value, as the reference returns it.  lr / wd are narrowed where ATen
 // narrows its Scalar arguments.
-__global__ __launch_bounds__(64) void k_sf_test_mapper(int E, int d, const float* __restrict__ phi,
-                                                       const float* __restrict__ r, float* __restrict__ W,
-                                                       int w_stride, float neg_lr, float wd,
-                                                       float* __restrict__ loss) {
-  const int e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= E) return;
-  const float* f = phi + (long long)e * d;
-  float* w = W + (long long)e * w_stride;
+// One row of it (shared by k_sf_test_mapper and the native test phase's k_test_intake, so the two
+// cannot drift): f = φ_e [d], w = w_e [d] updated in place; returns the pre-step loss.
+__device__ __forceinline__ float sf_test_mapper_row(int d, const float* f, float r, float* w, float neg_lr, float wd) {
   float y = 0.f;
   for (int k = 0; k < d; ++k) y = __builtin_fmaf(w[k], f[k], y);
-  const float diff = __fsub_rn(y, r[e]);
+  const float diff = __fsub_rn(y, r);
   const float gy = __fmul_rn(2.f, diff);
   for (int k = 0; k < d; ++k) {
     const float wk = w[k];
     const float dp = __fadd_rn(__fmul_rn(gy, f[k]), __fmul_rn(wd, wk));
     w[k] = __builtin_fmaf(neg_lr, dp, wk);
   }
-  loss[e] = __fmul_rn(diff, diff);
+  return __fmul_rn(diff, diff);
+}
+
+__global__ __launch_bounds__(64) void k_sf_test_mapper(int E, int d, const float* __restrict__ phi,
+                                                       const float* __restrict__ r, float* __restrict__ W,
+                                                       int w_stride, float neg_lr, float wd,
+                                                       float* __restrict__ loss) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= E) return;
+  loss[e] = sf_test_mapper_row(d, phi + (long long)e * d, r[e], W + (long long)e * w_stride, neg_lr, wd);
 }
 
 }  // namespace sfx

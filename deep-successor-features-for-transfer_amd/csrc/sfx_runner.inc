@@ -184,6 +184,25 @@ struct sfx_runner {
   std::vector<uint8_t> rec_stage;
   std::vector<long long> rec_meta;  // task, have, c, a_greedy, a_taken, terminal
 
+  // native test phase (sfx_runner_test_env / sfx_runner_test_phase): the test tasks' callbacks (null: the
+  // built-in synthetic test tasks, one generator each in trng), the exploration schedule's own stream,
+  // the host-coherent staging record and result, the device state block, selections, sequence word and
+  // the phase's loss block; allocated by the first phase
+  unsigned long long seed = 0;
+  sfx_env_reset_fn tenv_reset = nullptr;
+  sfx_env_step_fn tenv_step = nullptr;
+  void* tenv_ctx = nullptr;
+  std::vector<std::mt19937_64> trng;
+  std::mt19937_64 xrng;
+  uint8_t* tst = nullptr;
+  TestResult* tres = nullptr;
+  float* tS = nullptr;
+  int64_t* tsel = nullptr;
+  long long* tdseq = nullptr;
+  float* tloss = nullptr;
+  size_t tloss_n = 0;
+  long long tseq = 0;
+
   float uni() { return std::uniform_real_distribution<float>(0.f, 1.f)(rng); }
   // host-written cancel word next to the go word the gates poll (push: device memory through
   // the BAR; pull: host-coherent memory)
@@ -1162,6 +1181,8 @@ int sfx_runner_create(sfx_runner_t* out, sfx_t h, int batch, int capacity, float
   R->sel_use_gpi = sel_use_gpi ? 1 : 0;
   R->rng.seed(seed);
   R->irng.seed(seed ^ 0x5DEECE66DULL);
+  R->seed = seed;
+  R->xrng.seed(test_stream_seed(seed, -1));
   const char* eah = std::getenv("SFX_AHEAD");
   R->ahead_on = !(eah && eah[0] == '0');
   R->env_reset = reset_fn;
@@ -1244,6 +1265,10 @@ int sfx_runner_destroy(sfx_runner_t R) {
   if (R->dloss) (void)hipFree(R->dloss);
   if (R->dpush) (void)hipFree(R->dpush);
   if (R->dgo) (void)hipFree(R->dgo);
+  if (R->tst) (void)hipHostFree(R->tst);
+  if (R->tres) (void)hipHostFree(R->tres);
+  for (void* p : {(void*)R->tS, (void*)R->tsel, (void*)R->tdseq, (void*)R->tloss})
+    if (p) (void)hipFree(p);
   for (void* p : {(void*)R->drs, (void*)R->drs1, (void*)R->drphi, (void*)R->drr, (void*)R->drg, (void*)R->dra})
     if (p) (void)hipFree(p);
   delete R;
@@ -1534,6 +1559,243 @@ int runner_run(sfx_runner* R, int n) {
     }
   }
   return runner_complete(R);
+}
+
+// ---- native test phase (agents/sfdqn.py:105-120 over test_agent :139-166) ----
+
+int sfx_runner_test_env(sfx_runner_t R, sfx_env_reset_fn reset_fn, sfx_env_step_fn step_fn, void* ctx) {
+  if (!R) SFX_FAIL(SFX_E_ARG, "sfx_runner_test_env: null runner");
+  if ((!reset_fn) != (!step_fn)) SFX_FAIL(SFX_E_ARG, "sfx_runner_test_env: both test env callbacks or none");
+  R->tenv_reset = reset_fn;
+  R->tenv_step = step_fn;
+  R->tenv_ctx = reset_fn ? ctx : nullptr;
+  return SFX_OK;
+}
+
+namespace {
+
+// the phase's buffers: allocated here, never inside a capture
+int test_phase_buffers(sfx_runner* R, int E, int horizon) {
+  sfx_handle* h = R->h;
+  const TestStageLayout L = test_stage_layout(h->n_s, h->d);
+  if (!R->tst) {
+    if (hipHostMalloc((void**)&R->tst, L.bytes, hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess)
+      SFX_FAIL(SFX_E_HIP, "sfx_runner_test_phase: hipHostMalloc(staging) failed");
+    std::memset(R->tst, 0, L.bytes);
+  }
+  if (!R->tres) {
+    if (hipHostMalloc((void**)&R->tres, sizeof(TestResult), hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess)
+      SFX_FAIL(SFX_E_HIP, "sfx_runner_test_phase: hipHostMalloc(result) failed");
+    std::memset(R->tres, 0, sizeof(TestResult));
+  }
+  if (!R->tS) {
+    HIPCHK(hipMalloc((void**)&R->tS, sizeof(float) * TEST_EMAX * h->n_s));
+    HIPCHK(hipMemset(R->tS, 0, sizeof(float) * TEST_EMAX * h->n_s));
+  }
+  if (!R->tsel) {
+    HIPCHK(hipMalloc((void**)&R->tsel, sizeof(int64_t) * 2 * TEST_EMAX));
+    HIPCHK(hipMemset(R->tsel, 0, sizeof(int64_t) * 2 * TEST_EMAX));
+  }
+  if (!R->tdseq) {
+    HIPCHK(hipMalloc((void**)&R->tdseq, 64));
+    HIPCHK(hipMemset(R->tdseq, 0, 64));
+  }
+  const size_t need = (size_t)E * horizon;
+  if (R->tloss_n < need) {  // a larger block: the graphs keyed on the old one are never replayed again
+    if (R->tloss) (void)hipFree(R->tloss);
+    R->tloss = nullptr;
+    R->tloss_n = 0;
+    HIPCHK(hipMalloc((void**)&R->tloss, sizeof(float) * need));
+    R->tloss_n = need;
+  }
+  return SFX_OK;
+}
+
+// One lockstep step's launch set on h->stream: intake; when `full`, the forward of all heads on the
+// E rows chunked by max_batch (sfx_test_actions' launches), the GPI selection with per-row W, and
+// the publication.  The phase's trailing launch (the last transitions' updates) is the intake alone.
+int test_step_body(sfx_runner* R, int E, int horizon, float* W, int w_stride, bool full) {
+  sfx_handle* h = R->h;
+  const TestStageLayout L = test_stage_layout(h->n_s, h->d);
+  TestIntakeArgs A{};
+  A.stage = R->tst;
+  A.off_phi = L.phi;
+  A.off_s1 = L.s1;
+  A.E = E;
+  A.d = h->d;
+  A.n_s = h->n_s;
+  A.w_stride = w_stride;
+  A.horizon = horizon;
+  A.W = W;
+  A.S = R->tS;
+  A.loss = R->tloss;
+  A.dseq = R->tdseq;
+  hipLaunchKernelGGL(k_test_intake, dim3(1), dim3(256), 0, h->stream, A);
+  LAUNCHCHK();
+  if (!full) return SFX_OK;
+  for (int row0 = 0; row0 < E; row0 += h->Mmax) {
+    const int m = E - row0 < h->Mmax ? E - row0 : h->Mmax;
+    RC(run_fwd(h, {{R_G, P_ONLINE, 1, 0, h->T}}, m, R->tS + (size_t)row0 * h->n_s, nullptr));
+    GpiArgs g = gpi_args(R_G, 0, row0, W, nullptr, nullptr, nullptr, nullptr, R->tsel, 0, 1, m);
+    g.w_stride = w_stride;
+    g.sel_stride = 2;
+    RC(run_gpi(h, g));
+  }
+  hipLaunchKernelGGL(k_test_publish, dim3(1), dim3(128), 0, h->stream, (const int64_t*)R->tsel, E,
+                     (const long long*)R->tdseq, R->tres);
+  LAUNCHCHK();
+  return SFX_OK;
+}
+
+// cached per (E, w_stride, W, horizon's loss block): at most two graphs a phase (full / trailing)
+int test_step_launch(sfx_runner* R, int E, int horizon, float* W, int w_stride, bool full) {
+  sfx_handle* h = R->h;
+  const GraphKey key = make_key(27, {E, w_stride, horizon, full ? 1 : 0}, h->mask,
+                                {W, R->tst, R->tres, R->tS, R->tsel, R->tloss, R->tdseq});
+  return run_graph(h, key, [&]() -> int { return test_step_body(R, E, horizon, W, w_stride, full); });
+}
+
+// Wait (bounded by sfx_runner_wait_timeout) for launch set `seq` to publish its selections.
+int test_wait(sfx_runner* R, long long seq) {
+  const auto t0 = std::chrono::steady_clock::now();
+  long spins = 0;
+  while (__atomic_load_n(&R->tres->seq, __ATOMIC_ACQUIRE) < seq) {
+    if ((++spins & 1023) == 0) {
+      const double el = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+      if (el > R->wait_bound) {
+        char msg[160];
+        std::snprintf(msg, sizeof(msg), "sfx_runner_test_phase: lockstep launch %lld did not publish within %.3g s", seq,
+                      R->wait_bound);
+        (void)stream_drain(R->h->stream, std::max(30.0, R->wait_bound));
+        SFX_FAIL(SFX_E_STATE, msg);
+      }
+    }
+  }
+  return SFX_OK;
+}
+
+int test_env_reset(sfx_runner* R, int e, float* s0) {
+  if (R->tenv_reset) {
+    if (R->tenv_reset(R->tenv_ctx, e, s0)) SFX_FAIL(SFX_E_STATE, "sfx_runner_test_phase: test env reset callback failed");
+    return SFX_OK;
+  }
+  std::normal_distribution<float> nd(0.f, 1.f);
+  for (int k = 0; k < R->h->n_s; ++k) s0[k] = nd(R->trng[e]);
+  return SFX_OK;
+}
+
+// built-in synthetic test task e: the training synthetic task's shape (synth_step) on its own generator
+int test_env_step(sfx_runner* R, int e, int a, float* s1, float* phi, float* r, int* terminal) {
+  if (R->tenv_step) {
+    if (R->tenv_step(R->tenv_ctx, e, a, s1, phi, r, terminal))
+      SFX_FAIL(SFX_E_STATE, "sfx_runner_test_phase: test env step callback failed");
+    return SFX_OK;
+  }
+  std::mt19937_64& g = R->trng[e];
+  std::normal_distribution<float> nd(0.f, 1.f);
+  std::uniform_real_distribution<float> u01(0.f, 1.f);
+  const int d = R->h->d;
+  for (int k = 0; k < R->h->n_s; ++k) s1[k] = nd(g);
+  for (int k = 0; k < d; ++k) phi[k] = u01(g);
+  *r = phi[e % d];
+  *terminal = 0;  // never ends, like tasks/reacher.py:112
+  return SFX_OK;
+}
+
+int test_phase_run(sfx_runner* R, int E, int horizon, float test_epsilon, double lr, double wd, float* W, int w_stride,
+                   const int* explore, double* returns, double* loss, long long* steps, long long* actions) {
+  sfx_handle* h = R->h;
+  std::vector<int> drawn;
+  if (!explore) {
+    drawn.resize((size_t)E * horizon);
+    draw_test_schedule(R->xrng, E, horizon, test_epsilon, h->A, drawn.data());
+    explore = drawn.data();
+  }
+  if (!R->tenv_step)
+    for (int e = (int)R->trng.size(); e < E; ++e) R->trng.emplace_back(test_stream_seed(R->seed, e));
+  RC(test_phase_buffers(R, E, horizon));
+  TestPhaseHost P;
+  std::vector<double> ret_tmp(E);
+  std::vector<long long> steps_tmp(E);
+  P.begin(E, horizon, h->n_s, h->d, R->tst, explore, returns ? returns : ret_tmp.data(), steps ? steps : steps_tmp.data(),
+          actions);
+  const float neg_lr = (float)(-lr), wdf = (float)wd;
+  for (int e = 0; e < E; ++e) RC(test_env_reset(R, e, P.s1_row(e)));
+  P.header(++R->tseq, 0, 0, neg_lr, wdf);
+  RC(test_step_launch(R, E, horizon, W, w_stride, true));
+  for (int j = 0; j < horizon; ++j) {
+    RC(test_wait(R, R->tseq));
+    for (int e = 0; e < E; ++e) {
+      if (!P.is_live(e)) {
+        P.idle(e);
+        continue;
+      }
+      const long long greedy = R->tres->sel[2 * e + 1];
+      if (greedy < 0 || greedy >= h->A) SFX_FAIL(SFX_E_STATE, "sfx_runner_test_phase: corrupt published action");
+      const int a = P.action(e, j, greedy);
+      float r = 0.f;
+      int term = 0;
+      RC(test_env_step(R, e, a, P.s1_row(e), P.phi_row(e), &r, &term));
+      P.took(e, j, a, r, term);
+    }
+    const bool last = P.end_step() == 0 || j + 1 == horizon;
+    P.header(++R->tseq, j, 1, neg_lr, wdf);
+    RC(test_step_launch(R, E, horizon, W, w_stride, !last));
+    if (last) break;
+  }
+  std::vector<float> lh((size_t)E * horizon);
+  HIPCHK(hipMemcpyAsync(lh.data(), R->tloss, sizeof(float) * lh.size(), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  if (loss)
+    for (int e = 0; e < E; ++e) {
+      double acc = 0.0;  // accum_loss += loss.item(), in step order
+      for (long long j = 0; j < P.steps[e]; ++j) acc += (double)lh[(size_t)j * E + e];
+      loss[e] = acc;
+    }
+  return SFX_OK;
+}
+
+}  // namespace
+
+int sfx_runner_test_phase(sfx_runner_t R, int E, int horizon, float test_epsilon, double lr, double wd, float* W_dev,
+                          int w_stride, const int* explore_host, double* returns_host, double* loss_host,
+                          long long* steps_host, long long* actions_host) {
+  if (!R) SFX_FAIL(SFX_E_ARG, "sfx_runner_test_phase: null runner");
+  sfx_handle* h = R->h;
+  if (E < 1 || E > TEST_EMAX)
+    SFX_FAIL(SFX_E_ARG, "sfx_runner_test_phase: E = " + std::to_string(E) + " test tasks, needs 1 <= E <= " +
+                            std::to_string(TEST_EMAX));
+  if (horizon < 1) SFX_FAIL(SFX_E_ARG, "sfx_runner_test_phase: horizon = " + std::to_string(horizon) + ", needs horizon >= 1");
+  if (!W_dev) SFX_FAIL(SFX_E_ARG, "sfx_runner_test_phase: W_dev is null");
+  if (w_stride < h->d)
+    SFX_FAIL(SFX_E_ARG, "sfx_runner_test_phase: w_stride = " + std::to_string(w_stride) + ", needs w_stride >= d = " +
+                            std::to_string(h->d));
+  if (!(test_epsilon >= 0.f && test_epsilon <= 1.f))
+    SFX_FAIL(SFX_E_ARG, "sfx_runner_test_phase: test_epsilon needs to be in [0, 1]");
+  if (explore_host)  // checked before the first step: a phase never stops after it has moved an env or a W row
+    for (size_t i = 0; i < (size_t)E * horizon; ++i)
+      if (explore_host[i] >= h->A)
+        SFX_FAIL(SFX_E_ARG, "sfx_runner_test_phase: explore_host holds an action >= A = " + std::to_string(h->A));
+  if (R->broken) SFX_FAIL(SFX_E_STATE, R->broken_why.c_str());
+  if (h->Tg != h->T) SFX_FAIL(SFX_E_STATE, "sfx_runner_test_phase: needs an unsharded handle");
+  if (R->schedule != RUN_ALL && R->schedule != RUN_ACTIVE)
+    SFX_FAIL(SFX_E_STATE, std::string("sfx_runner_test_phase: the SF agent's test phase runs with the all and active "
+                                      "schedules only, not with schedule ") +
+                              std::to_string(R->schedule) + " (" + RUN_NAMES[R->schedule] + ")");
+  if (R->feat)
+    SFX_FAIL(SFX_E_STATE, "sfx_runner_test_phase: a featurizer is set (sfx_runner_featurizer); clear it first");
+  RunnerScope scope(h);
+  RC(settle(h));
+  RC(runner_complete(R));
+  if (R->pre_n) SFX_FAIL(SFX_E_STATE, "sfx_runner_test_phase: a step is pre-launched");
+  const int rc = test_phase_run(R, E, horizon, test_epsilon, lr, wd, W_dev, w_stride, explore_host, returns_host,
+                                loss_host, steps_host, actions_host);
+  if (rc) {  // leave nothing of the phase queued: the staging and the caller's W are free again on return
+    const std::string e = g_err;
+    (void)stream_drain(h->stream, std::max(30.0, R->wait_bound));
+    g_err = e;
+  }
+  return rc;
 }
 
 int sfx_runner_action(sfx_runner_t R, int64_t* out_host) {

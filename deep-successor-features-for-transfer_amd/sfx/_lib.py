@@ -158,6 +158,8 @@ SIGNATURES = {
     "sfx_pre_features": (_I, [_VP, _VP, _VP, _VP, _I, _VP]),
     "sfx_pre_features_rows": (_I, [_VP, _VP, _VP, _VP, _I, _VP]),
     "sfx_runner_featurizer": (_I, [_VP, _VP]),
+    "sfx_runner_test_env": (_I, [_VP, _VP, _VP, _VP]),
+    "sfx_runner_test_phase": (_I, [_VP, _I, _I, _F, _D, _D, _VP, _I, _VP, _VP, _VP, _VP, _VP]),
 }
 
 # env callbacks of sfx_runner_create (include/sfx.h)

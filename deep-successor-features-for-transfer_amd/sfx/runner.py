@@ -58,6 +58,27 @@ class SynthHopper(SynthReacher):
         return s1, phi, r, bool(self.rng.random() < self.p_end)
 
 
+def draw_test_schedule(E: int, horizon: int, epsilon: float, n_actions: int) -> np.ndarray:
+    """The exploration schedule of E sequential test episodes of ``horizon`` steps, drawn from Python's ``random``
+    in the reference's order (SFDQN.get_test_action, agents/sfdqn.py:127-128: per step one ``random.random()``
+    and, when it is <= epsilon, one ``random.randrange(n_actions)``; task 0's steps, then task 1's, ...).  Entry
+    [e, j] is the explored action or -1 for a greedy step.  For ``NativeEnvLoop.test_phase(explore=...)``, so a
+    run keeps the reference's own random stream; the draws are ``sfx.lockstep``'s (one shared function)."""
+    from .lockstep import _draw_schedule
+
+    return np.asarray(_draw_schedule(int(E), int(horizon), float(epsilon), int(n_actions)),
+                      dtype=np.int32).reshape(int(E), int(horizon))
+
+
+def test_phase_steps(n_samples: int, n_test_ev: int) -> list:
+    """The training steps t of one task's ``n_samples`` after which SFDQN.train evaluates
+    (agents/sfdqn.py:105-111: ``if t % n_test_ev == 0``)."""
+    return list(range(0, int(n_samples), int(n_test_ev)))
+
+
+test_phase_steps.__test__ = False  # a helper, not a pytest case
+
+
 class Staging:
     """One pinned host buffer + one device buffer with typed views at fixed offsets."""
 
@@ -249,9 +270,13 @@ class NativeEnvLoop:
     net gives one row at a time; the env's and the replay's φ are never read.  "active" keeps its look-ahead,
     "tsf" does not look ahead meanwhile.  The loop keeps the engine alive; its parameters may change between
     runs, not during one.
+
+    The SF agent's test phase (agents/sfdqn.py:105-120) runs in the runner too, under "all" and "active":
+    ``set_test_env`` / ``test_phase`` step the test tasks of ``test_agent`` in lockstep between runs without
+    touching training, and ``train`` is SFDQN.train's loop over both.
     """
 
-    FIELDS = ("s", "s1", "phi", "a", "gamma", "snext", "phi1", "r1", "rb")
+    FIELDS =("s", "s1", "phi", "a", "gamma", "snext", "phi1", "r1", "rb")
     SCHEDULES = {"all": 0, "active": 1, "tsf": 2, "sharded": 3, "sharded_tsf": 4, "phi": 5, "tsf_phi": 6}
     PHI_SCHEDULES = ("phi", "tsf_phi")
 
@@ -265,7 +290,9 @@ class NativeEnvLoop:
 
         self.eng, self.B, self._lib, self._check, self._C = engine, batch, lib, check, C
         self._cbs = None
+        self._test_cbs = None
         self._featurizer = None
+        self.episode_len = episode_len
         reset_fn = step_fn = None
         if env is not None:
             n_s, d = engine.n_s, engine.d
@@ -372,6 +399,97 @@ class NativeEnvLoop:
 
     def run(self, n: int):
         self._check(self._lib.sfx_runner_run(self._r, n), "sfx_runner_run")
+
+    def set_test_env(self, env):
+        """sfx_runner_test_env: the test tasks' env of ``test_phase`` -- an object with ``reset(e) -> s0`` and
+        ``step(e, a) -> (s1, phi, r, done)`` (numpy / floats; e is the test-task index), called through C
+        callbacks like the training env's; None selects the built-in synthetic test tasks (the default).  The
+        training env is never used for a test task."""
+        C = self._C
+        if env is None:
+            self._check(self._lib.sfx_runner_test_env(self._r, None, None, None), "sfx_runner_test_env")
+            self._test_cbs = None
+            return
+        from ._lib import ENV_RESET_FN, ENV_STEP_FN
+
+        n_s, d = self.eng.n_s, self.eng.d
+
+        def _reset(_ctx, e, s0):
+            try:
+                np.ctypeslib.as_array(s0, shape=(n_s,))[:] = np.asarray(env.reset(e), dtype=np.float32).reshape(n_s)
+                return 0
+            except Exception:  # reported as a failed phase by libsfx
+                return 1
+
+        def _step(_ctx, e, a, s1, phi, r, term):
+            try:
+                ns, ph, rr, tt = env.step(e, a)
+                np.ctypeslib.as_array(s1, shape=(n_s,))[:] = np.asarray(ns, np.float32).reshape(n_s)
+                np.ctypeslib.as_array(phi, shape=(d,))[:] = np.asarray(ph, np.float32).reshape(d)
+                r[0] = float(rr)
+                term[0] = 1 if tt else 0
+                return 0
+            except Exception:
+                return 1
+
+        cbs = (ENV_RESET_FN(_reset), ENV_STEP_FN(_step))
+        self._check(self._lib.sfx_runner_test_env(self._r, C.cast(cbs[0], C.c_void_p), C.cast(cbs[1], C.c_void_p),
+                                                  None), "sfx_runner_test_env")
+        self._test_cbs = cbs  # kept alive while the runner may call them
+
+    def test_phase(self, W, horizon=None, test_epsilon: float = 0.03, lr: float = 0.005, wd: float = 0.01,
+                   explore=None, want_actions: bool = False):
+        """sfx_runner_test_phase: ``[test_agent(task_e, e) for e in range(E)]`` of agents/sfdqn.py:139-166 with the
+        E episodes in lockstep inside the runner (between runs).  W: a contiguous float32 device tensor
+        [E, >= d], row e the test task's bias-free Linear(d, 1), updated in place.  horizon: steps per episode
+        (default: the loop's episode_len, the reference's agent.T).  explore: None (the runner draws the
+        ε-schedule from its own stream) or an int array [E, horizon] of explored actions, -1 = greedy
+        (``draw_test_schedule`` keeps the reference's own ``random`` stream).  lr / wd: the SGD step of
+        update_test_reward_mapper (:168-184).  Returns numpy ``(returns, loss_sums, steps)`` -- float64 [E],
+        float64 [E], int64 [E] -- and, with want_actions, the taken actions int64 [E, horizon] (-1 once a row
+        ended).  Training state is not touched: the next ``run`` continues as if no phase had run."""
+        C, e = self._C, self.eng
+        if not (isinstance(W, torch.Tensor) and W.dtype == torch.float32 and W.dim() == 2 and W.is_contiguous()
+                and W.device == torch.device(e.device)):
+            raise ValueError(f"W: a contiguous float32 tensor [E, >= d] on {e.device}")
+        E, stride = int(W.shape[0]), int(W.shape[1])
+        horizon = int(self.episode_len if horizon is None else horizon)
+        ex = None
+        if explore is not None:
+            ex = np.ascontiguousarray(np.asarray(explore, dtype=np.int32))
+            if ex.shape != (E, horizon):
+                raise ValueError(f"explore: an int array [{E}, {horizon}]")
+        n = max(E, 1)
+        ret, loss = np.zeros(n, np.float64), np.zeros(n, np.float64)
+        steps = np.zeros(n, np.int64)
+        acts = np.full((n, max(horizon, 1)), -1, np.int64) if want_actions else None
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None  # noqa: E731
+        self._check(self._lib.sfx_runner_test_phase(self._r, E, horizon, float(test_epsilon), float(lr), float(wd),
+                                                    W.data_ptr(), stride, ptr(ex), ptr(ret), ptr(loss), ptr(steps),
+                                                    ptr(acts)), "sfx_runner_test_phase")
+        out = (ret[:E], loss[:E], steps[:E])
+        return out + (acts[:E, :horizon],) if want_actions else out
+
+    def train(self, tasks, n_samples: int, W, n_test_ev: int = 1000, cycles_per_task: int = 1, **test_kwargs):
+        """SFDQN.train's loop (agents/sfdqn.py:102-123) on the runner: for every cycle and every training task
+        (``tasks``: the task indices, or their number), ``set_task`` and ``n_samples`` env steps, with a test phase
+        (``test_phase(W, **test_kwargs)``) after each training step t with ``t % n_test_ev == 0`` -- after step 1,
+        step n_test_ev + 1, ...  Returns ``return_data``: per phase the float32 mean of the E returns, as
+        ``torch.mean(torch.Tensor(Rs))`` gives.  All ``cycles_per_task`` cycles run: the reference returns from
+        inside its cycle loop after the first one, which is a bug and is not copied."""
+        idx = list(range(tasks)) if isinstance(tasks, int) else [int(t) for t in tasks]
+        return_data = []
+        for _ in range(int(cycles_per_task)):
+            for index in idx:
+                self.set_task(index)
+                done = 0
+                for t in test_phase_steps(n_samples, n_test_ev):
+                    self.run(t + 1 - done)
+                    done = t + 1
+                    Rs = self.test_phase(W, **test_kwargs)[0]
+                    return_data.append(torch.mean(torch.Tensor(Rs.tolist())).numpy()[()])
+                self.run(n_samples - done)
+        return return_data
 
     def action(self):
         out = (self._C.c_int64 * 3)()

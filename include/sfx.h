@@ -446,6 +446,48 @@ int sfx_runner_nonfinite(sfx_runner_t r, long long* steps);
 /* SF.gpi_counters (features/successor.py:270-272): [T][T] counts of the GPI task per active task
  * (counted only with GPI action selection, as SF.GPI(update_counters=use_gpi), agents/sfdqn.py:41) */
 int sfx_runner_gpi_counters(sfx_runner_t r, long long* out_host /* [T*T] */);
+/*
+ * The SF agent's test phase in the runner (replaces the evaluation block of SFDQN.train,
+ * agents/sfdqn.py:105-120: every n_test_ev training steps, test_agent (:139-166) on every test task),
+ * with the E episodes stepped together and no Python in the loop.
+ *
+ * sfx_runner_test_env: the test tasks' env callbacks; `task` is the test-task index e and the step's
+ *   terminal output is test_agent's `done` (agents/sfdqn.py:148, :160-161).  Both NULL (the default):
+ *   built-in synthetic test tasks of the training synthetic task's shape (s ~ N(0,1), φ ~ U[0,1),
+ *   r = φ[e % d], never done), each on a generator of its own seeded from (runner seed, a fixed
+ *   test-phase constant, e) -- the training env's stream is never touched, and the training
+ *   callbacks and their ctx are never used for a test task.
+ *
+ * sfx_runner_test_phase: [test_agent(task_e, e) for e < E] in lockstep.  Row e owns the bias-free
+ *   Linear(d, 1) W_dev + e * w_stride (caller-owned device memory, updated in place, exactly as by
+ *   sfx_test_reward_updates).  Step j of row e takes explore_host[e * horizon + j] when that is >= 0
+ *   (the explored action of get_test_action, agents/sfdqn.py:125-130), else the greedy GPI action of
+ *   sfx_test_actions under the current W[e] (:131-137); then the env steps and the SGD step of
+ *   update_test_reward_mapper (:168-184; lr, wd: the reference's 0.005 and 0.01) follows.
+ *   explore_host NULL: the runner draws the schedule up front from a test-phase stream of its own in
+ *   the reference's order -- task-major, per step one uniform and, when it is <= test_epsilon, one
+ *   randrange(A) (:127-128).  A row whose callback reports done still gets that step's update and then
+ *   stops, as the reference's break (:160-161): its W, return, loss sum and step count no longer change.
+ *   Outputs (host; any may be NULL): returns_host [E] the sum of the callbacks' float32 rewards in step
+ *   order, added in double (:158); loss_host [E] the sum of the float32 pre-step losses in step order
+ *   (accum_loss += loss.item(), :152-153); steps_host [E] the steps each row took; actions_host
+ *   [E * horizon] the taken actions, -1 after a row ended.
+ *   One lockstep step is one cached launch set on the handle's stream -- intake of the E transitions
+ *   (state block, mapper step, loss into a device [horizon][E] block read once at the end), forward of
+ *   all heads on the E rows in chunks of max_batch, GPI selection per row, publication to host-coherent
+ *   memory -- issued after the host has written the step's staging record; the host's wait for the
+ *   published selections is bounded by sfx_runner_wait_timeout (SFX_E_STATE past it).  Nothing waits
+ *   on the device for the host.  Rows that ended are still forwarded and then ignored.
+ *   Call between runs: unsharded handle, schedule 0 or 1, no featurizer, 1 <= E <= 64, horizon >= 1,
+ *   w_stride >= d, test_epsilon in [0, 1], explore_host entries < A; otherwise SFX_E_ARG / SFX_E_STATE
+ *   naming the limit, with nothing launched.  The phase does not touch the heads, their Adam state, w,
+ *   the target counters, the replay ring, the training env's episode, the training random streams or
+ *   the GPI counters: the next sfx_runner_run continues exactly as if the phase had not run.
+ */
+int sfx_runner_test_env(sfx_runner_t r, sfx_env_reset_fn reset_fn, sfx_env_step_fn step_fn, void* ctx);
+int sfx_runner_test_phase(sfx_runner_t r, int E, int horizon, float test_epsilon, double lr, double wd, float* W_dev,
+                          int w_stride, const int* explore_host, double* returns_host, double* loss_host,
+                          long long* steps_host, long long* actions_host);
 /* test hooks: keep the input record and (task, have_batch, c, greedy a, taken a, terminal) of
  * the next `capacity` steps */
 int sfx_runner_record(sfx_runner_t r, int capacity);
