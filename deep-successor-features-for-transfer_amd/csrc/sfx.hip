@@ -1389,6 +1389,17 @@ bool wait_posted(sfx_handle* h) {
   return true;
 }
 
+// The speculation verdict `flag` read after r rounds: the first policy of Tn whose next actions are
+// unverified (Tn: none).  Range-checked, then clamped by the test hook (sfx_debug_force_rerun: treat
+// the rounds as failed from this policy on) while the rounds it forces last -- r <= spec_rounds + 1;
+// the read after the device rounds passes r = spec_rounds.
+int spec_verdict(const sfx_handle* h, int flag, int Tn, int r, int* first) {
+  if (flag < 0 || flag > Tn) SFX_FAIL(SFX_E_STATE, "corrupt speculation flag");
+  const int f = h->force_rerun_from;
+  *first = f >= 0 && r <= h->spec_rounds + 1 && f < flag ? f : flag;
+  return SFX_OK;
+}
+
 // sfx_update_all returns once its step is enqueued; the speculation verdict -- and host rounds,
 // should the device rounds leave a policy unverified -- is collected by the next API call on the
 // handle (every entry point settles first), so the host never waits on a step it has not asked
@@ -1966,9 +1977,7 @@ int sfx_step_finish(sfx_t h, int64_t* out_host) {
   if (!p.posted || !wait_posted(h)) HIPCHK(hipEventSynchronize(h->ev_step));
   int first = h->T, dev_flag = h->T;
   if (p.update) {
-    first = p.use_gpi ? h->hout->flag : h->T;
-    if (first < 0 || first > h->T) SFX_FAIL(SFX_E_STATE, "corrupt speculation flag");
-    if (h->force_rerun_from >= 0 && h->force_rerun_from < first) first = h->force_rerun_from;
+    RC(spec_verdict(h, p.use_gpi ? h->hout->flag : h->T, h->T, h->spec_rounds, &first));
     int r = p.use_gpi ? h->spec_rounds : 1;
     dev_flag = first;
     h->steps_spec += 1;
@@ -1983,9 +1992,7 @@ int sfx_step_finish(sfx_t h, int64_t* out_host) {
       HIPCHK(hipMemcpyAsync(h->hout, h->dout, sizeof(StepOut), hipMemcpyDeviceToHost, h->stream));
       HIPCHK(hipStreamSynchronize(h->stream));
       ++r;
-      first = h->hout->flag;
-      if (first < 0 || first > h->T) SFX_FAIL(SFX_E_STATE, "corrupt speculation flag");
-      if (h->force_rerun_from >= 0 && r <= h->spec_rounds + 1 && h->force_rerun_from < first) first = h->force_rerun_from;
+      RC(spec_verdict(h, h->hout->flag, h->T, r, &first));
     }
     h->rounds_total += r;
     h->mask ^= h->all_bits();

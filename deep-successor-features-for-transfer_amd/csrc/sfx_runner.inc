@@ -239,6 +239,37 @@ struct RunnerScope {
   RunnerScope& operator=(const RunnerScope&) = delete;
 };
 
+// Points the handle at a step's host rounds and puts it back on every exit: the side stream (the
+// next step may already wait at its gate on the step stream), the step's slot mask and role copy,
+// the rounds' collectives on their own communicator (sharded), and a cancel word that stays zero
+// -- the next step's gate, spinning meanwhile, may write dcancel (when the host is slower than its
+// bound), but these rounds belong to a step that runs.
+struct RoundsTarget {
+  sfx_handle* h;
+  const hipStream_t stream;
+  const unsigned long long mask;
+  const int* const cancel;
+  const int mb;
+  const bool rounds_comm;
+  RoundsTarget(sfx_runner* R, unsigned long long m, int par)
+      : h(R->h), stream(h->stream), mask(h->mask), cancel(h->G.cancel), mb(h->G.mb), rounds_comm(h->rounds_comm) {
+    h->stream = R->side;
+    h->mask = m;
+    h->G.mb = par ? R_NS : 0;
+    h->G.cancel = h->dcancel + 1;
+    h->rounds_comm = R->schedule == RUN_SHARD;
+  }
+  ~RoundsTarget() {
+    h->stream = stream;
+    h->mask = mask;
+    h->G.cancel = cancel;
+    h->G.mb = mb;
+    h->rounds_comm = rounds_comm;
+  }
+  RoundsTarget(const RoundsTarget&) = delete;
+  RoundsTarget& operator=(const RoundsTarget&) = delete;
+};
+
 int synth_reset(sfx_runner* R, float* s0) {
   std::normal_distribution<float> nd(0.f, 1.f);
   for (int k = 0; k < R->h->n_s; ++k) s0[k] = nd(R->rng);
@@ -769,6 +800,18 @@ int round_wait(sfx_runner* R) {
   return hipStreamSynchronize(h->stream) == hipSuccess ? SFX_OK : SFX_E_HIP;
 }
 
+// Host round r of the step p on h->stream (launch_it false: its capture alone), the round of the
+// runner's schedule: all-task, or sharded with the round's finish
+int host_round(sfx_runner* R, const sfx_handle::Pending& p, int r, bool launch_it = true) {
+  sfx_handle* h = R->h;
+  if (R->schedule != RUN_SHARD)
+    return host_round_graph(R, 40, r, [&]() -> int { return launch_round(h, p, r, true); }, launch_it);
+  return host_round_graph(R, 41, r, [&]() -> int {
+    RC(shard_round_body(h, p, r, true));
+    return shard_final_body(h, p, r, nullptr, nullptr);
+  }, launch_it);
+}
+
 // Instantiate the host-round graphs a run may need (sfx_runner_warm): both slot masks, both round
 // parities, both role copies, with and without the look-ahead -- so the first step that needs host
 // rounds does not pay a capture on its critical path.
@@ -777,11 +820,8 @@ int warm_host_rounds(sfx_runner* R, unsigned long long bits, bool ahd) {
   if (R->schedule != RUN_ALL && R->schedule != RUN_SHARD) return SFX_OK;
   const unsigned long long m0 = h->mask;
   const sfx_runner::StepFlags fl0 = R->inflight_fl;
-  hipStream_t st0 = h->stream;
   int rc = SFX_OK;
-  h->stream = R->side;
-  h->G.cancel = h->dcancel + 1;
-  h->rounds_comm = R->schedule == RUN_SHARD;
+  const RoundsTarget target(R, m0, 0);
   for (int pm = 0; pm < 2 && rc == SFX_OK; ++pm)
     for (int ah = 0; ah < (ahd ? 2 : 1) && rc == SFX_OK; ++ah)
       for (int par = 0; par < (ah ? 2 : 1) && rc == SFX_OK; ++par)
@@ -789,22 +829,97 @@ int warm_host_rounds(sfx_runner* R, unsigned long long bits, bool ahd) {
           h->mask = pm ? m0 ^ bits : m0;
           R->inflight_fl = sfx_runner::StepFlags{false, ah != 0, par};
           h->G.mb = par ? R_NS : 0;
-          const sfx_handle::Pending p = runner_pending(R, true, false, ah != 0);
-          if (R->schedule == RUN_ALL)
-            rc = host_round_graph(R, 40, r, [&]() -> int { return launch_round(h, p, r, true); }, false);
-          else
-            rc = host_round_graph(R, 41, r, [&]() -> int {
-              RC(shard_round_body(h, p, r, true));
-              return shard_final_body(h, p, r, nullptr, nullptr);
-            }, false);
+          rc = host_round(R, runner_pending(R, true, false, ah != 0), r, false);
         }
-  h->mask = m0;
   R->inflight_fl = fl0;
-  h->stream = st0;
-  h->G.cancel = h->dcancel;
-  h->G.mb = 0;
-  h->rounds_comm = false;
   return rc;
+}
+
+// The hold word raised for a step's host rounds (runner_hold_for_rounds) and dropped on every exit.
+struct RoundsHold {
+  sfx_runner* R;
+  const bool drained;
+  explicit RoundsHold(sfx_runner* r) : R(r), drained(runner_hold_for_rounds(r)) {}
+  ~RoundsHold() { runner_hold(R, 0); }
+  RoundsHold(const RoundsHold&) = delete;
+  RoundsHold& operator=(const RoundsHold&) = delete;
+};
+
+// Finish the in-flight all-task step (RUN_ALL, RUN_SHARD) from the verdict `flag` its device rounds
+// published: account the speculation and, when it left policies unverified, run host rounds on the
+// side stream until none is (on every rank alike, sharded: the flag comes from all-reduced maxima),
+// then take the selection (*c, *a) from the last round.  The two schedules differ in recompute()
+// and host_round() alone (and in the refusal below).
+int runner_host_rounds(sfx_runner* R, int flag, long long* c, long long* a) {
+  sfx_handle* h = R->h;
+  const bool shard = R->schedule == RUN_SHARD;
+  const int Tn = shard ? h->Tg : h->T;
+  int first, r = h->spec_rounds;
+  RC(spec_verdict(h, flag, Tn, r, &first));
+  h->steps_spec += 1;
+  if (first == Tn) {
+    h->rounds_total += r;
+    return SFX_OK;
+  }
+  h->steps_fallback += 1;
+  h->policies_rerun += Tn - first;
+  R->host_rounds += 1;
+  // the step's own forward is recomputed in full (after a drain), its final rounds look ahead
+  const sfx_handle::Pending p = runner_pending(R, true, false, R->inflight_fl.ahead);
+  // The step's forward and device rounds again, from the pre-step slot (nothing of them committed
+  // there; this step's LMS has, so none here); sharded: round 0's maxima refilled as the gate fills them
+  const auto recompute = [&]() -> int {
+    if (!shard) return launch_step_all(h, p, -1, nullptr, nullptr, 0.f, h->spec_rounds);
+    const GateArgs g = runner_gate(R);
+    if (g.clr && hipMemsetD32Async((hipDeviceptr_t)g.clr, SORT_EMPTY, (size_t)g.nclr, h->stream) != hipSuccess)
+      return SFX_E_HIP;
+    RC(shard_begin_body(h, p, -1, nullptr, nullptr, 0.f));
+    for (int rr = 0; rr < h->spec_rounds; ++rr) RC(shard_round_body(h, p, rr, rr == h->spec_rounds - 1));
+    return shard_final_body(h, p, h->spec_rounds - 1, nullptr, nullptr);
+  };
+  const RoundsHold hold(R);  // before the handle leaves the step stream: a drain works on that one
+  if (shard && hold.drained && coll_active(h))  // a recompute would repeat its collectives on this rank only
+    SFX_FAIL(SFX_E_STATE, "runner: a sharded step needing host rounds found later steps cancelled at their gates");
+  const RoundsTarget target(R, R->inflight_mask, R->inflight_fl.par);
+  const int rc = [&]() -> int {
+    if (hold.drained) {
+      // cancelled steps ran over this step's transient buffers (activations, maxima, next actions):
+      // recompute it with the Adam step counters back at their pre-step values (round 0 bumps them)
+      int e = hipMemcpyAsync(h->step, h->host_step.data(), sizeof(int) * h->T, hipMemcpyHostToDevice, h->stream) == hipSuccess
+                  ? recompute()
+                  : SFX_E_HIP;
+      if (e == SFX_OK && (hipMemcpyAsync(h->hout, h->dout, sizeof(StepOut), hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
+                          hipStreamSynchronize(h->stream) != hipSuccess))
+        e = SFX_E_HIP;
+      if (e == SFX_OK) e = spec_verdict(h, h->hout->flag, Tn, r, &first);
+      R->recomputed += 1;
+      RC(e);
+    }
+    while (first < Tn) {  // each round fixes >= 1 head
+      if (r > Tn + 1) SFX_FAIL(SFX_E_STATE, "speculation did not converge");
+      RC(host_round(R, p, r));
+      RC(round_wait(R));  // the sharded round posts no verdict: the wait is for the stream
+      ++r;
+      RC(spec_verdict(h, h->hout->flag, Tn, r, &first));
+    }
+    return SFX_OK;
+  }();
+  if (rc) {
+    if (g_err.empty()) g_err = "runner: host round failed";
+    return rc;
+  }
+  *c = h->hout->sel[0];
+  *a = h->hout->sel[1];
+  h->rounds_total += r;
+  return SFX_OK;
+}
+
+// account head t's optimizer step exactly like sfx_step_finish
+int runner_account(sfx_runner* R, int t) {
+  after_update(R->h, t);
+  RC(maybe_sync_target(R->h, t));  // only reached with nothing pre-launched (see runner_run)
+  if (R->h->since_target[t] == 0) R->chain = false;  // the look-ahead forwarded the old target head
+  return SFX_OK;
 }
 
 // Wait for the in-flight step's result; finish a failed speculation with host rounds;
@@ -847,184 +962,11 @@ int runner_complete(sfx_runner* R) {
     SFX_FAIL(SFX_E_STATE, msg);
   }
   long long c = res->sel0, a = res->sel1;
-  if (R->inflight_have && R->schedule == RUN_SHARD) {
-    int first = res->flag;
-    if (first < 0 || first > h->Tg) SFX_FAIL(SFX_E_STATE, "corrupt speculation flag");
-    if (h->force_rerun_from >= 0 && h->force_rerun_from < first) first = h->force_rerun_from;
-    int r = h->spec_rounds;
-    h->steps_spec += 1;
-    if (first < h->Tg) {  // further rounds, on every rank alike (the flag comes from all-reduced maxima)
-      h->steps_fallback += 1;
-      h->policies_rerun += h->Tg - first;
-      R->host_rounds += 1;
-      // the step's own forward is recomputed in full (after a drain), its final rounds look ahead
-      const sfx_handle::Pending p = runner_pending(R, true, false, R->inflight_fl.ahead);
-      const unsigned long long saved_mask = h->mask;
-      hipStream_t saved_stream = h->stream;
-      h->mask = R->inflight_mask;
-      h->G.mb = R->inflight_fl.par ? R_NS : 0;
-      const bool drained = runner_hold_for_rounds(R);
-      if (drained && coll_active(h)) {  // a recompute would repeat its collectives on this rank only
-        h->mask = saved_mask;
-        runner_hold(R, 0);
-        SFX_FAIL(SFX_E_STATE, "runner: a sharded step needing host rounds found later steps cancelled at their gates");
-      }
-      h->stream = R->side;            // the next step may already wait at its gate
-      h->G.cancel = h->dcancel + 1;   // see the all-task host rounds below
-      h->rounds_comm = true;          // the rounds' collectives on their own communicator
-      int rc = SFX_OK;
-      if (drained) {
-        // one rank without collectives: the all-task recompute below -- the cancelled steps ran over
-        // this step's transient buffers (activations, maxima, next actions), so its forward and device
-        // rounds run again from the pre-step slot (no LMS: it committed), the Adam step counters back
-        // at their pre-step values and round 0's maxima refilled as the gate fills them
-        if (hipMemcpyAsync(h->step, h->host_step.data(), sizeof(int) * h->T, hipMemcpyHostToDevice, h->stream) !=
-            hipSuccess)
-          rc = SFX_E_HIP;
-        const GateArgs g = runner_gate(R);
-        if (rc == SFX_OK && g.clr &&
-            hipMemsetD32Async((hipDeviceptr_t)g.clr, SORT_EMPTY, (size_t)g.nclr, h->stream) != hipSuccess)
-          rc = SFX_E_HIP;
-        if (rc == SFX_OK) rc = shard_begin_body(h, p, -1, nullptr, nullptr, 0.f);
-        for (int rr = 0; rr < h->spec_rounds && rc == SFX_OK; ++rr)
-          rc = shard_round_body(h, p, rr, rr == h->spec_rounds - 1);
-        if (rc == SFX_OK) rc = shard_final_body(h, p, h->spec_rounds - 1, nullptr, nullptr);
-        if (rc == SFX_OK && hipMemcpyAsync(h->hout, h->dout, sizeof(StepOut), hipMemcpyDeviceToHost, h->stream) != hipSuccess)
-          rc = SFX_E_HIP;
-        if (rc == SFX_OK && hipStreamSynchronize(h->stream) != hipSuccess) rc = SFX_E_HIP;
-        if (rc == SFX_OK) {
-          first = h->hout->flag;
-          if (first < 0 || first > h->Tg) {
-            g_err = "corrupt speculation flag";
-            rc = SFX_E_STATE;
-          }
-          if (h->force_rerun_from >= 0 && h->force_rerun_from < first) first = h->force_rerun_from;
-        }
-        R->recomputed += 1;
-      }
-      while (first < h->Tg && rc == SFX_OK) {
-        if (r > h->Tg + 1) {
-          g_err = "speculation did not converge";
-          rc = SFX_E_STATE;
-          break;
-        }
-        rc = host_round_graph(R, 41, r, [&]() -> int {
-          RC(shard_round_body(h, p, r, true));
-          return shard_final_body(h, p, r, nullptr, nullptr);
-        });
-        if (rc == SFX_OK && hipStreamSynchronize(h->stream) != hipSuccess) rc = SFX_E_HIP;
-        ++r;
-        if (rc == SFX_OK) first = h->hout->flag;
-        if (rc == SFX_OK && (first < 0 || first > h->Tg)) {
-          g_err = "corrupt speculation flag";
-          rc = SFX_E_STATE;
-        }
-        if (h->force_rerun_from >= 0 && r <= h->spec_rounds + 1 && h->force_rerun_from < first) first = h->force_rerun_from;
-      }
-      h->mask = saved_mask;
-      h->stream = saved_stream;
-      h->G.cancel = h->dcancel;
-      h->G.mb = 0;
-      h->rounds_comm = false;
-      runner_hold(R, 0);
-      if (rc) {
-        if (g_err.empty()) g_err = "runner: host round failed";
-        return rc;
-      }
-      c = h->hout->sel[0];
-      a = h->hout->sel[1];
-    }
-    h->rounds_total += r;
-    for (int t = 0; t < h->T; ++t) {
-      after_update(h, t);
-      RC(maybe_sync_target(h, t));  // only reached with nothing pre-launched (see runner_run)
-      if (h->since_target[t] == 0) R->chain = false;  // the look-ahead forwarded the old target heads
-    }
-  } else if (R->inflight_have && R->schedule != RUN_ALL) {
-    const int loc = own_loc(R);  // sharded TSF: only the owner of the active task updated
-    if (loc >= 0) {
-      after_update(h, loc);
-      RC(maybe_sync_target(h, loc));  // only reached with nothing pre-launched (see runner_run)
-      if (h->since_target[loc] == 0) R->chain = false;  // the look-ahead forwarded the old target head
-    }
-  } else if (R->inflight_have) {
-    int first = res->flag;
-    if (first < 0 || first > h->T) SFX_FAIL(SFX_E_STATE, "corrupt speculation flag");
-    // test hook (sfx_debug_force_rerun): treat the device rounds as failed from this policy on
-    if (h->force_rerun_from >= 0 && h->force_rerun_from < first) first = h->force_rerun_from;
-    int r = h->spec_rounds;
-    h->steps_spec += 1;
-    if (first < h->T) {
-      h->steps_fallback += 1;
-      h->policies_rerun += h->T - first;
-      R->host_rounds += 1;
-      // the step's own forward is recomputed in full (after a drain), its final rounds look ahead
-      const sfx_handle::Pending p = runner_pending(R, true, false, R->inflight_fl.ahead);
-      hipStream_t saved_stream = h->stream;
-      const unsigned long long saved_mask = h->mask;
-      const bool drained = runner_hold_for_rounds(R);
-      h->stream = R->side;
-      h->mask = R->inflight_mask;
-      h->G.mb = R->inflight_fl.par ? R_NS : 0;
-      // the next step's gate, spinning meanwhile, may write the cancel word (when the host is
-      // slower than its bound): these rounds belong to a step that runs, so they read a zero word
-      h->G.cancel = h->dcancel + 1;
-      int rc = SFX_OK;
-      if (drained) {
-        // cancelled steps ran over this step's transient buffers: recompute its forward and device
-        // rounds from the pre-step slot (nothing of them committed there; this step's LMS has, so
-        // none here) with the Adam step counters back at their pre-step values (round 0 bumps them)
-        if (hipMemcpyAsync(h->step, h->host_step.data(), sizeof(int) * h->T, hipMemcpyHostToDevice, h->stream) !=
-            hipSuccess)
-          rc = SFX_E_HIP;
-        if (rc == SFX_OK) rc = launch_step_all(h, p, -1, nullptr, nullptr, 0.f, h->spec_rounds);
-        if (rc == SFX_OK && hipMemcpyAsync(h->hout, h->dout, sizeof(StepOut), hipMemcpyDeviceToHost, h->stream) != hipSuccess)
-          rc = SFX_E_HIP;
-        if (rc == SFX_OK && hipStreamSynchronize(h->stream) != hipSuccess) rc = SFX_E_HIP;
-        if (rc == SFX_OK) {
-          first = h->hout->flag;
-          if (first < 0 || first > h->T) {
-            g_err = "corrupt speculation flag";
-            rc = SFX_E_STATE;
-          }
-          if (h->force_rerun_from >= 0 && h->force_rerun_from < first) first = h->force_rerun_from;
-        }
-        R->recomputed += 1;
-      }
-      while (first < h->T && rc == SFX_OK) {
-        if (r > h->T + 1) {
-          g_err = "speculation did not converge";
-          rc = SFX_E_STATE;
-          break;
-        }
-        rc = host_round_graph(R, 40, r, [&]() -> int { return launch_round(h, p, r, true); });
-        if (rc == SFX_OK) rc = round_wait(R);
-        ++r;
-        if (rc == SFX_OK) first = h->hout->flag;
-        if (rc == SFX_OK && (first < 0 || first > h->T)) {
-          g_err = "corrupt speculation flag";
-          rc = SFX_E_STATE;
-        }
-        if (h->force_rerun_from >= 0 && r <= h->spec_rounds + 1 && h->force_rerun_from < first) first = h->force_rerun_from;
-      }
-      h->stream = saved_stream;
-      h->mask = saved_mask;
-      h->G.cancel = h->dcancel;
-      h->G.mb = 0;
-      runner_hold(R, 0);
-      if (rc) {
-        if (g_err.empty()) g_err = "runner: host round failed";
-        return rc;
-      }
-      c = h->hout->sel[0];
-      a = h->hout->sel[1];
-    }
-    h->rounds_total += r;
-    for (int t = 0; t < h->T; ++t) {
-      after_update(h, t);
-      RC(maybe_sync_target(h, t));  // only reached with nothing pre-launched (see runner_run)
-      if (h->since_target[t] == 0) R->chain = false;  // the look-ahead forwarded the old target heads
-    }
+  if (R->inflight_have && (R->schedule == RUN_ALL || R->schedule == RUN_SHARD)) {
+    RC(runner_host_rounds(R, res->flag, &c, &a));
+    for (int t = 0; t < h->T; ++t) RC(runner_account(R, t));
+  } else if (R->inflight_have && own_loc(R) >= 0) {  // sharded TSF: only the owner of the active task updated
+    RC(runner_account(R, own_loc(R)));
   }
   R->sel_c = c;
   R->sel_a = a;
@@ -1090,6 +1032,18 @@ int runner_issue(sfx_runner* R, bool have, bool lms, const sfx_runner::StepFlags
   R->inflight_have = have;
   R->inflight_lms = lms;
   R->inflight_seq = R->seq;
+  return SFX_OK;
+}
+
+// Launch ONE graph of the next `span` steps behind the in-flight one (their gates wait for the
+// host) and queue their flags (see runner_launch)
+int runner_prelaunch(sfx_runner* R, bool next_have, bool lms, int span, sfx_runner::StepFlags fl0) {
+  RC(runner_launch(R, next_have, lms, span, true, fl0));
+  R->pre_n = span;
+  R->pre_have = next_have;
+  R->prelaunched += span;
+  for (int st = 0; st < span; ++st)
+    R->preq.push_back({st == 0 ? fl0.pre : fl0.ahead, fl0.ahead, fl0.ahead ? (fl0.par + st) & 1 : 0});
   return SFX_OK;
 }
 
@@ -1457,11 +1411,7 @@ int runner_run(sfx_runner* R, int n) {
     RC(runner_complete(R));  // the greedy action for R->s
     if (shard_coll && R->pipeline && !h->prof && h->use_graphs && coll_capturable(h) && R->pre_n == 0) {
       const bool next_have = std::min<long>(R->rsize + 1, R->cap) >= R->B;
-      RC(runner_launch(R, next_have, true, 1));
-      R->pre_n = 1;
-      R->pre_have = next_have;
-      R->prelaunched += 1;
-      R->preq.push_back({false, false, 0});
+      RC(runner_prelaunch(R, next_have, true, 1, {false, false, 0}));
     }
     const long long c = R->sel_c;
     // SF.GPI(..., update_counters=self.use_gpi) (agents/sfdqn.py:41): counted only with GPI selection
@@ -1549,12 +1499,7 @@ int runner_run(sfx_runner* R, int n) {
         while (span < span_max && next_have && i + span + 1 < n && upd + span < left &&
                (!ahd || !plan_of(R, R->cur_step + 1 + span).dirty))
           ++span;
-        RC(runner_launch(R, next_have, R->schedule == RUN_ALL || shard, span, true, fl0));
-        R->pre_n = span;
-        R->pre_have = next_have;
-        R->prelaunched += span;
-        for (int st = 0; st < span; ++st)
-          R->preq.push_back({st == 0 ? fl0.pre : fl0.ahead, fl0.ahead, fl0.ahead ? (fl0.par + st) & 1 : 0});
+        RC(runner_prelaunch(R, next_have, R->schedule == RUN_ALL || shard, span, fl0));
       }
     }
   }
