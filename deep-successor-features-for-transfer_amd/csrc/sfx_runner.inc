@@ -202,6 +202,12 @@ struct sfx_runner {
   float* tloss = nullptr;
   size_t tloss_n = 0;
   long long tseq = 0;
+  // the TSF agent's phase (sfx_runner_tsf_test_phase): its own staging record (TsfTestStageLayout), device
+  // block (TsfTestDevLayout) and [horizon][E][3] loss block; result, selections and sequence word are shared
+  uint8_t* ttst = nullptr;
+  uint8_t* ttblk = nullptr;
+  float* ttloss = nullptr;
+  size_t ttloss_n = 0;
 
   float uni() { return std::uniform_real_distribution<float>(0.f, 1.f)(rng); }
   // host-written cancel word next to the go word the gates poll (push: device memory through
@@ -213,6 +219,10 @@ struct sfx_runner {
 namespace {
 
 int shard_tsf_body(sfx_runner* R, bool have, bool pre, bool ahead);  // sfx_tsf.inc
+int tsf_test_phase_ready(sfx_handle* h, int E);
+int tsf_test_phase_body(sfx_runner* R, int E, int horizon, float* W, int w_stride, float* Om, int o_stride, float* mom,
+                        int mom_stride);
+const void* tsf_test_phase_tgf(sfx_handle* h);
 int shard_tsf_buffers(sfx_handle* h);
 
 bool sharded_sched(const sfx_runner* R) { return R->schedule == RUN_SHARD || R->schedule == RUN_SHARD_TSF; }
@@ -1221,7 +1231,8 @@ int sfx_runner_destroy(sfx_runner_t R) {
   if (R->dgo) (void)hipFree(R->dgo);
   if (R->tst) (void)hipHostFree(R->tst);
   if (R->tres) (void)hipHostFree(R->tres);
-  for (void* p : {(void*)R->tS, (void*)R->tsel, (void*)R->tdseq, (void*)R->tloss})
+  if (R->ttst) (void)hipHostFree(R->ttst);
+  for (void* p : {(void*)R->tS, (void*)R->tsel, (void*)R->tdseq, (void*)R->tloss, (void*)R->ttblk, (void*)R->ttloss})
     if (p) (void)hipFree(p);
   for (void* p : {(void*)R->drs, (void*)R->drs1, (void*)R->drphi, (void*)R->drr, (void*)R->drg, (void*)R->dra})
     if (p) (void)hipFree(p);
@@ -1519,6 +1530,24 @@ int sfx_runner_test_env(sfx_runner_t R, sfx_env_reset_fn reset_fn, sfx_env_step_
 
 namespace {
 
+// what the SF and the TSF phase share: the published result, the device selections and the sequence word
+int test_phase_shared_buffers(sfx_runner* R) {
+  if (!R->tres) {
+    if (hipHostMalloc((void**)&R->tres, sizeof(TestResult), hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess)
+      SFX_FAIL(SFX_E_HIP, "sfx_runner_test_phase: hipHostMalloc(result) failed");
+    std::memset(R->tres, 0, sizeof(TestResult));
+  }
+  if (!R->tsel) {
+    HIPCHK(hipMalloc((void**)&R->tsel, sizeof(int64_t) * 2 * TEST_EMAX));
+    HIPCHK(hipMemset(R->tsel, 0, sizeof(int64_t) * 2 * TEST_EMAX));
+  }
+  if (!R->tdseq) {
+    HIPCHK(hipMalloc((void**)&R->tdseq, 64));
+    HIPCHK(hipMemset(R->tdseq, 0, 64));
+  }
+  return SFX_OK;
+}
+
 // the phase's buffers: allocated here, never inside a capture
 int test_phase_buffers(sfx_runner* R, int E, int horizon) {
   sfx_handle* h = R->h;
@@ -1528,22 +1557,10 @@ int test_phase_buffers(sfx_runner* R, int E, int horizon) {
       SFX_FAIL(SFX_E_HIP, "sfx_runner_test_phase: hipHostMalloc(staging) failed");
     std::memset(R->tst, 0, L.bytes);
   }
-  if (!R->tres) {
-    if (hipHostMalloc((void**)&R->tres, sizeof(TestResult), hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess)
-      SFX_FAIL(SFX_E_HIP, "sfx_runner_test_phase: hipHostMalloc(result) failed");
-    std::memset(R->tres, 0, sizeof(TestResult));
-  }
+  RC(test_phase_shared_buffers(R));
   if (!R->tS) {
     HIPCHK(hipMalloc((void**)&R->tS, sizeof(float) * TEST_EMAX * h->n_s));
     HIPCHK(hipMemset(R->tS, 0, sizeof(float) * TEST_EMAX * h->n_s));
-  }
-  if (!R->tsel) {
-    HIPCHK(hipMalloc((void**)&R->tsel, sizeof(int64_t) * 2 * TEST_EMAX));
-    HIPCHK(hipMemset(R->tsel, 0, sizeof(int64_t) * 2 * TEST_EMAX));
-  }
-  if (!R->tdseq) {
-    HIPCHK(hipMalloc((void**)&R->tdseq, 64));
-    HIPCHK(hipMemset(R->tdseq, 0, 64));
   }
   const size_t need = (size_t)E * horizon;
   if (R->tloss_n < need) {  // a larger block: the graphs keyed on the old one are never replayed again
@@ -1736,6 +1753,183 @@ int sfx_runner_test_phase(sfx_runner_t R, int E, int horizon, float test_epsilon
   const int rc = test_phase_run(R, E, horizon, test_epsilon, lr, wd, W_dev, w_stride, explore_host, returns_host,
                                 loss_host, steps_host, actions_host);
   if (rc) {  // leave nothing of the phase queued: the staging and the caller's W are free again on return
+    const std::string e = g_err;
+    (void)stream_drain(h->stream, std::max(30.0, R->wait_bound));
+    g_err = e;
+  }
+  return rc;
+}
+
+// ---- the TSF agent's test phase (agents/tsfdqn_sequential.py:363-369 over test_agent :392-433) ----
+
+namespace {
+
+// the TSF phase's buffers: allocated here, never inside a capture
+int tsf_test_phase_buffers(sfx_runner* R, int E, int horizon) {
+  sfx_handle* h = R->h;
+  RC(test_phase_shared_buffers(R));
+  if (!R->ttst) {
+    const TsfTestStageLayout L = tsf_test_stage_layout(h->n_s, h->d);
+    if (hipHostMalloc((void**)&R->ttst, L.bytes, hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess)
+      SFX_FAIL(SFX_E_HIP, "sfx_runner_tsf_test_phase: hipHostMalloc(staging) failed");
+    std::memset(R->ttst, 0, L.bytes);
+  }
+  if (!R->ttblk) {
+    const TsfTestDevLayout D = tsf_test_dev_layout(h->n_s, h->d);
+    HIPCHK(hipMalloc((void**)&R->ttblk, D.bytes));
+    HIPCHK(hipMemset(R->ttblk, 0, D.bytes));
+  }
+  const size_t need = (size_t)E * horizon * 3;
+  if (R->ttloss_n < need) {  // a larger block: the graphs keyed on the old one are never replayed again
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (R->ttloss) (void)hipFree(R->ttloss);
+    R->ttloss = nullptr;
+    R->ttloss_n = 0;
+    HIPCHK(hipMalloc((void**)&R->ttloss, sizeof(float) * need));
+    R->ttloss_n = need;
+  }
+  return SFX_OK;
+}
+
+// cached per (E, strides, horizon, the caller's blocks, the phase's buffers): one graph a phase
+int tsf_test_step_launch(sfx_runner* R, int E, int horizon, float* W, int w_stride, float* Om, int o_stride, float* mom,
+                         int mom_stride) {
+  sfx_handle* h = R->h;
+  const GraphKey key = make_key(28, {E, w_stride, o_stride, mom_stride, horizon}, h->mask,
+                                {W, Om, mom, R->ttst, R->tres, R->ttblk, R->ttloss, R->tsel, R->tdseq, tsf_test_phase_tgf(h)});
+  return run_graph(h, key, [&]() -> int {
+    return tsf_test_phase_body(R, E, horizon, W, w_stride, Om, o_stride, mom, mom_stride);
+  });
+}
+
+int tsf_test_phase_run(sfx_runner* R, int E, int horizon, float test_epsilon, const sfx_tsf_test_hp& hp, float* W,
+                       int w_stride, float* Om, int o_stride, float* mom, int mom_stride, long long* opt_steps,
+                       const int* explore, double* returns, double* losses, long long* steps, long long* actions) {
+  sfx_handle* h = R->h;
+  std::vector<int> drawn;
+  if (!explore) {
+    drawn.resize((size_t)E * horizon * 2);
+    draw_tsf_test_schedule(R->xrng, E, horizon, test_epsilon, h->A, drawn.data());
+    explore = drawn.data();
+  }
+  if (!R->tenv_step)
+    for (int e = (int)R->trng.size(); e < E; ++e) R->trng.emplace_back(test_stream_seed(R->seed, e));
+  RC(tsf_test_phase_buffers(R, E, horizon));
+  TsfTestPhaseHost P;
+  std::vector<double> ret_tmp(E);
+  std::vector<long long> steps_tmp(E);
+  TsfTestRowHP rhp;
+  rhp.lr_w = (float)hp.lr_w;
+  rhp.wd_w = (float)hp.wd_w;
+  rhp.wd_omega = (float)hp.wd_omega;
+  rhp.lr_omega = hp.lr_omega;
+  rhp.lr_omega_decay = hp.lr_omega_decay;
+  P.begin(E, horizon, h->n_s, h->d, R->ttst, explore, rhp, hp.gamma, hp.beta, hp.lasso, opt_steps,
+          returns ? returns : ret_tmp.data(), steps ? steps : steps_tmp.data(), actions);
+  const auto launch_step = [&]() -> int {
+    return tsf_test_step_launch(R, E, horizon, W, w_stride, Om, o_stride, mom, mom_stride);
+  };
+  // the a1 the device chose for the rows of the record just published (step j)
+  const auto collect_a1 = [&](int j) -> int {
+    for (int e = 0; e < E; ++e) {
+      if (!P.in_record(e)) continue;
+      const long long a1 = R->tres->sel[2 * e];
+      if (a1 < 0 || a1 >= h->A) SFX_FAIL(SFX_E_STATE, "sfx_runner_tsf_test_phase: corrupt published action");
+      P.took_a1(e, j, a1);
+    }
+    return SFX_OK;
+  };
+  for (int e = 0; e < E; ++e) RC(test_env_reset(R, e, P.s1_row(e)));
+  P.header(++R->tseq, 0, 0);
+  RC(launch_step());
+  int last_j = -1;
+  for (int j = 0; j < horizon; ++j) {
+    RC(test_wait(R, R->tseq));
+    if (j > 0) RC(collect_a1(j - 1));
+    for (int e = 0; e < E; ++e) {
+      if (!P.is_live(e)) {
+        P.idle(e);
+        continue;
+      }
+      const long long greedy = R->tres->sel[2 * e + 1];
+      if (greedy < 0 || greedy >= h->A) SFX_FAIL(SFX_E_STATE, "sfx_runner_tsf_test_phase: corrupt published action");
+      const int a = P.action(e, j, greedy);
+      float r = 0.f;
+      int term = 0;
+      RC(test_env_step(R, e, a, P.s1_row(e), P.phi_row(e), &r, &term));
+      P.took(e, j, a, r, term);
+    }
+    const bool last = P.end_step() == 0 || j + 1 == horizon;
+    P.header(++R->tseq, j, 1);
+    RC(launch_step());
+    last_j = j;
+    if (last) break;
+  }
+  RC(test_wait(R, R->tseq));
+  RC(collect_a1(last_j));
+  std::vector<float> lh((size_t)E * horizon * 3);
+  HIPCHK(hipMemcpyAsync(lh.data(), R->ttloss, sizeof(float) * lh.size(), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  if (losses)
+    for (int e = 0; e < E; ++e)
+      for (int c = 0; c < 3; ++c) {
+        double acc = 0.0;  // accum_loss += loss_t.item() and its siblings, in step order
+        for (long long j = 0; j < P.steps[e]; ++j) acc += (double)lh[((size_t)j * E + e) * 3 + c];
+        losses[(size_t)e * 3 + c] = acc;
+      }
+  return SFX_OK;
+}
+
+}  // namespace
+
+float sfx_tsf_test_lr_omega(double lr_omega, double decay, long long epoch) {
+  return tsf_test_lr_omega(lr_omega, decay, epoch);
+}
+
+int sfx_runner_tsf_test_phase(sfx_runner_t R, int E, int horizon, float test_epsilon, const sfx_tsf_test_hp* hp,
+                              float* W_dev, int w_stride, float* Omega_dev, int o_stride, float* adam_state_dev,
+                              int mom_stride, long long* opt_steps_host, const int* explore_host, double* returns_host,
+                              double* losses_host, long long* steps_host, long long* actions_host) {
+  const std::string F = "sfx_runner_tsf_test_phase: ";
+  if (!R) SFX_FAIL(SFX_E_ARG, F + "null runner");
+  sfx_handle* h = R->h;
+  if (E < 1 || E > TEST_EMAX)
+    SFX_FAIL(SFX_E_ARG, F + "E = " + std::to_string(E) + " test tasks, needs 1 <= E <= min(" + std::to_string(TEST_EMAX) +
+                            ", max_batch = " + std::to_string(h->Mmax) + ")");
+  if (!hp || !W_dev || !Omega_dev || !adam_state_dev || !opt_steps_host)
+    SFX_FAIL(SFX_E_ARG, F + "hp, W_dev, Omega_dev, adam_state_dev and opt_steps_host need to be non-null");
+  if (horizon < 1) SFX_FAIL(SFX_E_ARG, F + "horizon = " + std::to_string(horizon) + ", needs horizon >= 1");
+  if (w_stride < h->d)
+    SFX_FAIL(SFX_E_ARG, F + "w_stride = " + std::to_string(w_stride) + ", needs w_stride >= d = " + std::to_string(h->d));
+  if (o_stride < h->T)
+    SFX_FAIL(SFX_E_ARG, F + "o_stride = " + std::to_string(o_stride) + ", needs o_stride >= T = " + std::to_string(h->T));
+  if (mom_stride < 2 * (h->d + h->T))
+    SFX_FAIL(SFX_E_ARG, F + "mom_stride = " + std::to_string(mom_stride) + ", needs mom_stride >= 2(d + T) = " +
+                            std::to_string(2 * (h->d + h->T)));
+  if (!(test_epsilon >= 0.f && test_epsilon <= 1.f)) SFX_FAIL(SFX_E_ARG, F + "test_epsilon needs to be in [0, 1]");
+  for (int e = 0; e < E; ++e)
+    if (opt_steps_host[e] < 0 || opt_steps_host[e] + horizon >= (1LL << 24))
+      SFX_FAIL(SFX_E_ARG, F + "opt_steps_host[" + std::to_string(e) + "] = " + std::to_string(opt_steps_host[e]) +
+                              ", needs opt_steps >= 0 and opt_steps + horizon < 2^24");
+  if (explore_host)  // checked before the first step: a phase never stops after it has moved an env or a row
+    for (size_t i = 0; i < (size_t)E * horizon * 2; ++i)
+      if (explore_host[i] >= h->A)
+        SFX_FAIL(SFX_E_ARG, F + "explore_host holds an action >= A = " + std::to_string(h->A));
+  if (R->broken) SFX_FAIL(SFX_E_STATE, R->broken_why.c_str());
+  if (!h->tsf) SFX_FAIL(SFX_E_STATE, F + "call sfx_tsf_setup first (and load every g_t and h)");
+  if (R->schedule != RUN_TSF)
+    SFX_FAIL(SFX_E_STATE, F + "the TSF agent's test phase runs with the tsf schedule only, not with schedule " +
+                              std::to_string(R->schedule) + " (" + RUN_NAMES[R->schedule] + ")");
+  if (R->feat) SFX_FAIL(SFX_E_STATE, F + "a featurizer is set (sfx_runner_featurizer); clear it first");
+  RunnerScope scope(h);
+  RC(settle(h));
+  RC(runner_complete(R));
+  if (R->pre_n) SFX_FAIL(SFX_E_STATE, F + "a step is pre-launched");
+  RC(tsf_test_phase_ready(h, E));
+  const int rc = tsf_test_phase_run(R, E, horizon, test_epsilon, *hp, W_dev, w_stride, Omega_dev, o_stride,
+                                    adam_state_dev, mom_stride, opt_steps_host, explore_host, returns_host, losses_host,
+                                    steps_host, actions_host);
+  if (rc) {  // leave nothing of the phase queued: the staging and the caller's blocks are free again on return
     const std::string e = g_err;
     (void)stream_drain(h->stream, std::max(30.0, R->wait_bound));
     g_err = e;

@@ -80,4 +80,156 @@ __global__ __launch_bounds__(128) void k_test_publish(const int64_t* sel, int E,
   }
 }
 
+// -------------------------------------------------------------------------------------
+// The TSF agent's test phase (sfx_runner_tsf_test_phase): E episodes of
+// agents/tsfdqn_sequential.py:392-433 in lockstep.  One lockstep step is k_tsf_test_intake -> one ψ
+// forward of the E rows (ψ(S), ψ(S1) online, ψ⁻(S1)) -> k_tsf_test_g -> k_tsf_test_row ->
+// k_test_publish, a linear chain; the staging record is TsfTestStageLayout's (sfx_test_host.h).
+// -------------------------------------------------------------------------------------
+
+// what the intake leaves on the device for the row kernel
+struct TsfTestDevHdr {
+  int step, update;
+  float gamma, beta, lasso;
+  int pad_[3];
+};
+
+// The phase's device block, one allocation: byte offsets of its parts (multiples of 16)
+struct TsfTestDevLayout {
+  int hdr, live, a, a1x, rowp, phi, S, S1;
+  size_t bytes;
+};
+inline TsfTestDevLayout tsf_test_dev_layout(int n_s, int d) {
+  TsfTestDevLayout L{};
+  const auto up16 = [](size_t n) { return (n + 15) / 16 * 16; };
+  L.hdr = 0;
+  L.live = (int)sizeof(TsfTestDevHdr);
+  L.a = L.live + 4 * TEST_EMAX;
+  L.a1x = L.a + 8 * TEST_EMAX;
+  L.rowp = L.a1x + 4 * TEST_EMAX;
+  L.phi = L.rowp + 4 * 6 * TEST_EMAX;
+  L.S = L.phi + (int)up16(sizeof(float) * TEST_EMAX * (size_t)d);
+  L.S1 = L.S + (int)up16(sizeof(float) * TEST_EMAX * (size_t)n_s);
+  L.bytes = (size_t)L.S1 + up16(sizeof(float) * TEST_EMAX * (size_t)n_s);
+  return L;
+}
+
+struct TsfTestIntakeArgs {
+  const unsigned char* stage;  // host-coherent staging record (TsfTestStageLayout)
+  int off_phi, off_s1;         // byte offsets of φ and s1 in it (multiples of 16)
+  int E, d, n_s, horizon;
+  TsfTestDevHdr* hdr;
+  int* live;         // [E]
+  int64_t* a;        // [E] the actions taken at s (k_tsf_test_step's type)
+  int* a1x;          // [E] explored a1 or -1
+  float* rowp;       // [E][6]
+  float* phi;        // [E][d]
+  float* S;          // [E][n_s]: a live row's previous S1 row
+  float* S1;         // [E][n_s]: its new s1
+  long long* dseq;   // device: the header's seq, for k_test_publish
+};
+
+// (a) of a TSF lockstep step, one workgroup: for every live row the previous S1 row becomes its S row
+// and the record's s1 its S1 row; φ, a, the explored a1 and rowp go to the device block, the live
+// mask and the header's step / update / (γ, β, λ) too, the header's seq to the device word.  A row
+// that is not live keeps everything it had.
+__global__ __launch_bounds__(256) void k_tsf_test_intake(TsfTestIntakeArgs A) {
+  constexpr int PRE16 = TSF_TEST_PRE / 16;
+  __shared__ __attribute__((aligned(16))) uint4 s_pre[PRE16];
+  const int tid = threadIdx.x;
+  SFX_CHK(A.E >= 1 && A.E <= TEST_EMAX, A.E, TEST_EMAX, 0);
+  const uint4* src = reinterpret_cast<const uint4*>(A.stage);
+  if (tid < PRE16) s_pre[tid] = src[tid];
+  __syncthreads();
+  const TestStageHdr& H = *reinterpret_cast<const TestStageHdr*>(s_pre);
+  const float* hp = reinterpret_cast<const float*>(s_pre) + sizeof(TestStageHdr) / 4;
+  const int* live = reinterpret_cast<const int*>(hp + 4);
+  const int* a = live + 2 * TEST_EMAX;
+  const int* a1x = a + TEST_EMAX;
+  const float* rowp = reinterpret_cast<const float*>(a1x + TEST_EMAX);
+  const float* gphi = reinterpret_cast<const float*>(A.stage + A.off_phi);
+  const float* gs1 = reinterpret_cast<const float*>(A.stage + A.off_s1);
+  const FDiv fn = fdiv(A.n_s), fd = fdiv(A.d);
+  for (int i = tid; i < A.E * A.n_s; i += 256) {
+    const int e = i / fn;
+    SFX_CHK(e >= 0 && e < A.E, e, A.E, i);
+    if (live[e]) {
+      A.S[i] = A.S1[i];
+      A.S1[i] = gs1[i];
+    }
+  }
+  for (int i = tid; i < A.E * A.d; i += 256) {
+    const int e = i / fd;
+    SFX_CHK(e >= 0 && e < A.E, e, A.E, i);
+    if (live[e]) A.phi[i] = gphi[i];
+  }
+  for (int i = tid; i < A.E * 6; i += 256)
+    if (live[i / 6]) A.rowp[i] = rowp[i];
+  if (tid < A.E) {
+    A.live[tid] = live[tid];
+    if (live[tid]) {
+      A.a[tid] = a[tid];
+      A.a1x[tid] = a1x[tid];
+    }
+  }
+  if (tid == 0) {
+    SFX_CHK(!H.update || (H.step >= 0 && H.step < A.horizon), H.step, A.horizon, H.update);
+    TsfTestDevHdr d{H.step, H.update, hp[0], hp[1], hp[2], {0, 0, 0}};
+    *A.hdr = d;
+    __hip_atomic_store(A.dseq, H.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
+struct TsfTestRowArgs {
+  const TsfTestDevHdr* hdr;
+  const int* live;     // [E]
+  const int* a1x;      // [E] explored a1 or -1
+  const float* psi_s1; // ψ_t(s1) of the online heads: an activation role, as TsfTestArgs::psi
+  float* loss;         // [horizon][E][3]: loss, l2, l1 of each step's update
+  int64_t* sel;        // [E][2]: the step's a1, the next step's greedy action
+  int E, horizon;
+};
+
+// (c) of a TSF lockstep step, one workgroup per row; a row that is not live returns at once.  When
+// the header asks for an update: a1 = the explored one, or the greedy action at s1 under the row's
+// (w, ω) as they stand (tsf_test_greedy: k_tsf_test_act's arithmetic), then one
+// update_test_reward_mapper step with it (tsf_test_step_body: k_tsf_test_step's arithmetic, its losses
+// into loss[step][e]).  Then, for every live row, the greedy action at s1 under the updated (w, ω):
+// the action the row takes next unless it explores.  A0: sfx_tsf_test_updates' arguments (psi = ψ(S),
+// psi1 = ψ⁻(S1) of the E rows; gamma / beta / lasso / losses come from the device header).
+__global__ __launch_bounds__(256) void k_tsf_test_row(TsfTestArgs A0, TsfTestRowArgs X) {
+  const int e = blockIdx.x, tid = threadIdx.x;
+  SFX_CHK(e < X.E && X.E <= TEST_EMAX, e, X.E, 0);
+  if (!X.live[e]) return;
+  __shared__ float s_on[64];
+  __shared__ float s_q[256];
+  __shared__ int s_a1;
+  const TsfTestDevHdr H = *X.hdr;
+  A0.gamma = H.gamma;
+  A0.beta = H.beta;
+  A0.lasso = H.lasso;
+  const int step = H.update && H.step >= 0 && H.step < X.horizon ? H.step : 0;
+  A0.losses = X.loss + (size_t)step * X.E * 3;
+  const TsfTestArgs A = tsf_test_row(A0, e);
+  TsfTestArgs Ag = A;  // the greedy choice at s1
+  Ag.psi = X.psi_s1 + (long long)e * A.O;
+  if (H.update) {
+    SFX_CHK(H.step >= 0 && H.step < X.horizon, H.step, X.horizon, e);
+    const int x = X.a1x[e];
+    const int g = x >= 0 ? x : tsf_test_greedy(Ag, s_on, s_q);  // x is the workgroup's: a uniform branch
+    if (tid == 0) {
+      s_a1 = g;
+      X.sel[2 * e] = g;
+    }
+    __syncthreads();
+    const int a = (int)*A.a, a1 = s_a1;
+    SFX_CHK(a >= 0 && a < A.A && a1 >= 0 && a1 < A.A, a, a1, A.A);
+    tsf_test_step_body(A, a, a1);
+    __threadfence_block();  // the row's stores of w and ω: visible to the whole workgroup
+    __syncthreads();
+  }
+  const int best = tsf_test_greedy(Ag, s_on, s_q);
+  if (tid == 0) X.sel[2 * e + 1] = best;
+}
+
 }  // namespace sfx

@@ -1136,10 +1136,9 @@ __global__ __launch_bounds__(64) void k_tsf_test_g(TsfTestArgs A0) {
 }
 
 // The greedy test action: argmax_a Σ_k w_k Σ_t ω̂_t ψ_t(s)[a][k] (first index on ties), one WG.
-__global__ __launch_bounds__(256) void k_tsf_test_act(TsfTestArgs A0) {
-  const TsfTestArgs A = tsf_test_row(A0, blockIdx.x);
-  __shared__ float s_on[64];
-  __shared__ float s_q[256];
+// tsf_test_greedy is the whole workgroup's body (s_on [64], s_q [256] in LDS); thread 0 returns the
+// action.  k_tsf_test_act and the native test phase's row kernel (sfx_testphase.h) both call it.
+__device__ __forceinline__ int tsf_test_greedy(const TsfTestArgs& A, float* s_on, float* s_q) {
   const int tid = threadIdx.x, T = A.T, d = A.d;
   if (tid == 0) {
     float S = 0.f;
@@ -1157,23 +1156,31 @@ __global__ __launch_bounds__(256) void k_tsf_test_act(TsfTestArgs A0) {
     s_q[a] = q;
   }
   __syncthreads();
+  int best = 0;
   if (tid == 0) {
-    int best = 0;
     for (int a = 1; a < A.A; ++a)
       if (s_q[a] > s_q[best]) best = a;
-    *A.act_out = best;
   }
+  return best;
 }
 
-// One update_test_reward_mapper step, one WG (T <= 64, d <= 256, G <= 512).
-__global__ __launch_bounds__(256) void k_tsf_test_step(TsfTestArgs A0) {
+__global__ __launch_bounds__(256) void k_tsf_test_act(TsfTestArgs A0) {
   const TsfTestArgs A = tsf_test_row(A0, blockIdx.x);
+  __shared__ float s_on[64];
+  __shared__ float s_q[256];
+  const int best = tsf_test_greedy(A, s_on, s_q);
+  if (threadIdx.x == 0) *A.act_out = best;
+}
+
+// One update_test_reward_mapper step, one WG (T <= 64, d <= 256, G <= 512): tsf_test_step_body is the
+// whole workgroup's body for the transition's actions (a, a1); k_tsf_test_step reads them from
+// A.a / A.a1, the native test phase's row kernel (sfx_testphase.h) chooses a1 itself.
+__device__ __forceinline__ void tsf_test_step_body(const TsfTestArgs& A, const int a, const int a1) {
   const int tid = threadIdx.x, T = A.T, d = A.d, G = A.G;
   __shared__ float s_om[64], s_on[64], s_dn[64];
   __shared__ float s_ws[2][512], s_gws[512];
   __shared__ float s_tphi[256], s_de[256], s_gaff[256], s_w[256];
   __shared__ float s_S, s_rfit, s_l1, s_sumdn;
-  const int a = (int)*A.a, a1 = (int)*A.a1;
   const float* Wh = A.hp;
   const float* bh = A.hp + (long long)d * G;
   if (tid < T) s_om[tid] = A.omega[tid];
@@ -1276,6 +1283,11 @@ __global__ __launch_bounds__(256) void k_tsf_test_step(TsfTestArgs A0) {
     vo[tid] = vv;
     A.omega[tid] = fmaxf(pp, 1e-7f);
   }
+}
+
+__global__ __launch_bounds__(256) void k_tsf_test_step(TsfTestArgs A0) {
+  const TsfTestArgs A = tsf_test_row(A0, blockIdx.x);
+  tsf_test_step_body(A, (int)*A.a, (int)*A.a1);
 }
 
 }  // namespace sfx

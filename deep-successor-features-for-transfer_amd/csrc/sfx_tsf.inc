@@ -12,6 +12,8 @@ struct sfx_tsf_state {
   float* bimg = nullptr;  // the backward's staging image of W_l, W_h (TsfArgs::bimg)
   float* tgf = nullptr;  // [rows][T][2][G] g features of the test-task path (sfx_tsf_test_update(s))
   int tgf_rows = 0;
+  std::vector<char> g_loaded;  // task t's g_t was loaded (sfx_tsf_load_g / _g_state); h_loaded: sfx_tsf_load_h
+  bool h_loaded = false;
   // The TSF forward, backward and the flows' sums ride along in ψ launches on the step stream
   // (k_fwd_tsf / k_bwd_tsf) when their LDS carve and the grid fit, else they run as their own
   // launches there.  (Round 3's side-stream fork of the TSF kernels lost its A/B to riding along
@@ -291,6 +293,7 @@ int sfx_tsf_setup(sfx_t h, int G, int K, float beta, double lr_g, double wd_g, d
   s->Pg = (int)(nfl + nlin);
   s->Ph = d * G + d;
   s->beta = beta;
+  s->g_loaded.assign(h->T, 0);
   s->hpg = AdamHP{lr_g, wd_g, h->hp_psi.b1, h->hp_psi.b2, h->hp_psi.eps};
   s->hph = AdamHP{lr_h, wd_h, h->hp_psi.b1, h->hp_psi.b2, h->hp_psi.eps};
   const int T = h->T, R2 = 2 * B;
@@ -333,6 +336,7 @@ int sfx_tsf_load_g(sfx_t h, int t, const float* g_host) {
                         hipMemcpyHostToDevice, h->stream));
   RC(tsf_pack_chain(h, t));
   HIPCHK(hipStreamSynchronize(h->stream));
+  h->tsf->g_loaded[t] = 1;
   return SFX_OK;
 }
 
@@ -359,6 +363,7 @@ int sfx_tsf_load_g_state(sfx_t h, int t, const float* g_host, const float* gm_ho
   HIPCHK(hipMemcpyAsync(h->tsf->gv + o, gv_host, n, hipMemcpyHostToDevice, h->stream));
   RC(tsf_pack_chain(h, t));
   HIPCHK(hipStreamSynchronize(h->stream));
+  h->tsf->g_loaded[t] = 1;
   return SFX_OK;
 }
 
@@ -390,6 +395,7 @@ int sfx_tsf_load_h(sfx_t h, const float* h_host) {
   touch(h);
   HIPCHK(hipMemcpyAsync(h->tsf->hp, h_host, sizeof(float) * h->tsf->Ph, hipMemcpyHostToDevice, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
+  h->tsf->h_loaded = true;
   return SFX_OK;
 }
 
@@ -654,6 +660,103 @@ int tsf_test_ok(sfx_handle* h) {
   if (!h || !h->tsf) SFX_FAIL(SFX_E_ARG, "sfx_tsf_test_*: call sfx_tsf_setup first");
   if (h->Tg != h->T || h->T > 64 || h->d > 256 || h->tsf->G > 512 || h->A > 256)
     SFX_FAIL(SFX_E_ARG, "sfx_tsf_test_*: needs an unsharded handle, T <= 64, d <= 256, G <= 512, A <= 256");
+  return SFX_OK;
+}
+
+// ---- the TSF agent's test phase in the runner (sfx_runner_tsf_test_phase, sfx_runner.inc) ----
+
+// the handle's part of the phase's preconditions; sizes the g-feature scratch for E rows (never inside a capture)
+int tsf_test_phase_ready(sfx_handle* h, int E) {
+  if (!h->tsf) SFX_FAIL(SFX_E_STATE, "sfx_runner_tsf_test_phase: call sfx_tsf_setup first (and load every g_t and h)");
+  sfx_tsf_state* ts = h->tsf;
+  if (h->Tg != h->T) SFX_FAIL(SFX_E_STATE, "sfx_runner_tsf_test_phase: needs an unsharded handle");
+  if (h->T > 64 || h->d > 256 || ts->G > 512 || h->A > 256)
+    SFX_FAIL(SFX_E_ARG, "sfx_runner_tsf_test_phase: needs T <= 64, d <= 256, G <= 512, A <= 256");
+  for (int t = 0; t < h->T; ++t)
+    if (!ts->g_loaded[t])
+      SFX_FAIL(SFX_E_STATE, "sfx_runner_tsf_test_phase: g of task " + std::to_string(t) + " was never loaded (sfx_tsf_load_g)");
+  if (!ts->h_loaded) SFX_FAIL(SFX_E_STATE, "sfx_runner_tsf_test_phase: h was never loaded (sfx_tsf_load_h)");
+  if (E > h->Mmax)
+    SFX_FAIL(SFX_E_ARG, "sfx_runner_tsf_test_phase: E = " + std::to_string(E) + " test tasks, needs 1 <= E <= min(" +
+                            std::to_string(TEST_EMAX) + ", max_batch = " + std::to_string(h->Mmax) + ")");
+  if (ts->tgf_rows < E) {
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (ts->tgf) HIPCHK(hipFree(ts->tgf));
+    ts->tgf = nullptr;
+    ts->tgf_rows = 0;
+    HIPCHK(hipMalloc((void**)&ts->tgf, sizeof(float) * 2 * (size_t)E * h->T * ts->G));
+    ts->tgf_rows = E;
+  }
+  return SFX_OK;
+}
+
+const void* tsf_test_phase_tgf(sfx_handle* h) { return h->tsf ? h->tsf->tgf : nullptr; }
+
+// One lockstep step's launches on h->stream, a linear chain: intake; ψ(S) -> R_A, ψ(S1) -> R_V (online) and
+// ψ⁻(S1) -> R_G in one forward (none of them a role the look-ahead carries: R_NS* and the minibatch copy
+// R_S*); the g features of S / S1; the row kernel; the publication.
+int tsf_test_phase_body(sfx_runner* R, int E, int horizon, float* W, int w_stride, float* Om, int o_stride, float* mom,
+                        int mom_stride) {
+  sfx_handle* h = R->h;
+  sfx_tsf_state* ts = h->tsf;
+  const TsfTestStageLayout L = tsf_test_stage_layout(h->n_s, h->d);
+  const TsfTestDevLayout D = tsf_test_dev_layout(h->n_s, h->d);
+  uint8_t* blk = R->ttblk;
+  TsfTestIntakeArgs I{};
+  I.stage = R->ttst;
+  I.off_phi = L.phi;
+  I.off_s1 = L.s1;
+  I.E = E;
+  I.d = h->d;
+  I.n_s = h->n_s;
+  I.horizon = horizon;
+  I.hdr = reinterpret_cast<TsfTestDevHdr*>(blk + D.hdr);
+  I.live = reinterpret_cast<int*>(blk + D.live);
+  I.a = reinterpret_cast<int64_t*>(blk + D.a);
+  I.a1x = reinterpret_cast<int*>(blk + D.a1x);
+  I.rowp = reinterpret_cast<float*>(blk + D.rowp);
+  I.phi = reinterpret_cast<float*>(blk + D.phi);
+  I.S = reinterpret_cast<float*>(blk + D.S);
+  I.S1 = reinterpret_cast<float*>(blk + D.S1);
+  I.dseq = R->tdseq;
+  hipLaunchKernelGGL(k_tsf_test_intake, dim3(1), dim3(256), 0, h->stream, I);
+  LAUNCHCHK();
+  RC(run_fwd(h, {{R_A, P_ONLINE, 1, 0, h->T}, {R_V, P_ONLINE, 2, 0, h->T}, {R_G, P_TARGET, 2, 0, h->T}}, E, I.S, I.S1));
+  TsfTestArgs A = tsf_test_args(h);
+  A.s = I.S;
+  A.s1 = I.S1;
+  A.gfeat = ts->tgf;
+  A.psi = h->act + (size_t)R_A * h->T * h->actSize;
+  A.psi1 = h->act + (size_t)R_G * h->T * h->actSize;
+  A.phi = I.phi;
+  A.a = I.a;
+  A.w = W;
+  A.omega = Om;
+  A.mom = mom;
+  A.w_stride = w_stride;
+  A.o_stride = o_stride;
+  A.mom_stride = mom_stride;
+  A.rowp = I.rowp;
+  A.step = 1;  // per row from rowp
+  A.hpw = AdamHP{0.0, 0.0, h->hp_psi.b1, h->hp_psi.b2, h->hp_psi.eps};
+  A.hpo = A.hpw;
+  launch(h, K_TSF, 4.0 * E * ((double)h->T * ts->Pg + 2.0 * h->T * ts->G), k_tsf_test_g, dim3(h->T, E), dim3(64), A);
+  LAUNCHCHK();
+  TsfTestRowArgs X{};
+  X.hdr = I.hdr;
+  X.live = I.live;
+  X.a1x = I.a1x;
+  X.psi_s1 = h->act + (size_t)R_V * h->T * h->actSize;
+  X.loss = R->ttloss;
+  X.sel = R->tsel;
+  X.E = E;
+  X.horizon = horizon;
+  launch(h, K_TSF, 4.0 * E * (3.0 * h->T * h->O + 2.0 * h->T * ts->G + ts->Ph + 6.0 * (h->d + h->T)), k_tsf_test_row,
+         dim3(E), dim3(256), A, X);
+  LAUNCHCHK();
+  hipLaunchKernelGGL(k_test_publish, dim3(1), dim3(128), 0, h->stream, (const int64_t*)R->tsel, E,
+                     (const long long*)R->tdseq, R->tres);
+  LAUNCHCHK();
   return SFX_OK;
 }
 

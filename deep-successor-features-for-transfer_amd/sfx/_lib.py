@@ -160,7 +160,17 @@ SIGNATURES = {
     "sfx_runner_featurizer": (_I, [_VP, _VP]),
     "sfx_runner_test_env": (_I, [_VP, _VP, _VP, _VP]),
     "sfx_runner_test_phase": (_I, [_VP, _I, _I, _F, _D, _D, _VP, _I, _VP, _VP, _VP, _VP, _VP]),
+    "sfx_tsf_test_lr_omega": (_F, [_D, _D, C.c_longlong]),
+    "sfx_runner_tsf_test_phase": (_I, [_VP, _I, _I, _F, _VP, _VP, _I, _VP, _I, _VP, _I, _VP, _VP, _VP, _VP, _VP,
+                                       _VP]),
 }
+
+
+class TsfTestHP(C.Structure):
+    """sfx_tsf_test_hp (include/sfx.h): the hyperparameters of sfx_runner_tsf_test_phase."""
+    _fields_ = [("gamma", _F), ("beta", _F), ("lasso", _F), ("lr_w", _D), ("wd_w", _D), ("lr_omega", _D),
+                ("wd_omega", _D), ("lr_omega_decay", _D)]
+
 
 # env callbacks of sfx_runner_create (include/sfx.h)
 ENV_RESET_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_float))

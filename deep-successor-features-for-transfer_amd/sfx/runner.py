@@ -70,6 +70,24 @@ def draw_test_schedule(E: int, horizon: int, epsilon: float, n_actions: int) -> 
                       dtype=np.int32).reshape(int(E), int(horizon))
 
 
+def draw_tsf_test_schedule(E: int, horizon: int, epsilon: float, n_actions: int, diag: bool = False) -> np.ndarray:
+    """The exploration schedule of E sequential TSF test episodes of ``horizon`` steps, drawn from Python's
+    ``random`` in the reference's order (agents/tsfdqn_sequential.py:377-381 over :399-402: per step the draws of
+    ``get_test_action`` at s and then at s1, each one ``random.random()`` and, when it is <= epsilon, one
+    ``random.randrange(n_actions)``; task 0's steps, then task 1's, ...).  Entry [e, j] = (explored a, explored
+    a1), -1 for a greedy choice.  diag: also consume the binding's per-step diagnostic draw (:502), as
+    ``sfx.lockstep`` does for an agent that prints.  For ``NativeEnvLoop.tsf_test_phase(explore=...)``; the
+    draws are ``sfx.lockstep``'s (one shared function)."""
+    from . import lockstep
+
+    sched = lockstep._tsf_draw_schedule(int(E), int(horizon), float(epsilon), int(n_actions), bool(diag))
+    return np.asarray([[(xa, xa1) for xa, xa1, _ in row] for row in sched],
+                      dtype=np.int32).reshape(int(E), int(horizon), 2)
+
+
+TSF_TEST_HP = ("gamma", "beta", "lasso", "lr_w", "wd_w", "lr_omega", "wd_omega", "lr_omega_decay")
+
+
 def test_phase_steps(n_samples: int, n_test_ev: int) -> list:
     """The training steps t of one task's ``n_samples`` after which SFDQN.train evaluates
     (agents/sfdqn.py:105-111: ``if t % n_test_ev == 0``)."""
@@ -273,7 +291,9 @@ class NativeEnvLoop:
 
     The SF agent's test phase (agents/sfdqn.py:105-120) runs in the runner too, under "all" and "active":
     ``set_test_env`` / ``test_phase`` step the test tasks of ``test_agent`` in lockstep between runs without
-    touching training, and ``train`` is SFDQN.train's loop over both.
+    touching training, and ``train`` is SFDQN.train's loop over both.  Under "tsf" the TSF agent's test phase
+    (agents/tsfdqn_sequential.py:392-433) does: ``tsf_test_phase`` steps the test tasks in lockstep, each with its
+    own (w, ω), Adam moments and ω-lr schedule, and ``train`` evaluates with it.
     """
 
     FIELDS =("s", "s1", "phi", "a", "gamma", "snext", "phi1", "r1", "rb")
@@ -470,15 +490,69 @@ class NativeEnvLoop:
         out = (ret[:E], loss[:E], steps[:E])
         return out + (acts[:E, :horizon],) if want_actions else out
 
+    def tsf_test_phase(self, W, Omega, adam_state, opt_steps, hp, horizon=None, test_epsilon: float = 0.03,
+                       explore=None, want_actions: bool = False):
+        """sfx_runner_tsf_test_phase: ``[test_agent(task_e, e) for e in range(E)]`` of
+        agents/tsfdqn_sequential.py:392-433 with the E episodes in lockstep inside the runner (schedule "tsf",
+        between runs).  Row e of the contiguous float32 device tensors is test task e's state, updated in place:
+        W [E, >= d] its reward weights, Omega [E, >= T] its ω, adam_state [E, >= 2(d + T)] the Adam moments
+        (m_w, v_w, m_ω, v_ω; zeros before the first phase).  opt_steps: an int64 numpy array [E], the optimizer
+        steps (= scheduler epochs) each task's optimizer has taken, advanced in place -- keep the four across
+        phases, as the reference keeps every test task's optimizer and scheduler.  hp: a dict of gamma, beta,
+        lasso, lr_w, wd_w, lr_omega, wd_omega, lr_omega_decay (ω's lr at epoch k is lr_omega (1 - decay)^k).
+        explore: None (the runner draws the ε-schedule from its own stream) or an int array [E, horizon, 2] of
+        the explored (a, a1), -1 = greedy (``draw_tsf_test_schedule`` keeps the reference's own ``random``
+        stream).  Returns numpy ``(returns, losses, steps)`` -- float64 [E], float64 [E, 3] the sums of (loss,
+        l2, l1), int64 [E] -- and, with want_actions, the taken (a, a1) int64 [E, horizon, 2] (-1 once a row
+        ended).  Training state is not touched: the next ``run`` continues as if no phase had run."""
+        from ._lib import TsfTestHP
+
+        C, e = self._C, self.eng
+        for name, t in (("W", W), ("Omega", Omega), ("adam_state", adam_state)):
+            if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.dim() == 2 and t.is_contiguous()
+                    and t.device == torch.device(e.device)):
+                raise ValueError(f"{name}: a contiguous float32 tensor [E, ...] on {e.device}")
+        E = int(W.shape[0])
+        if int(Omega.shape[0]) != E or int(adam_state.shape[0]) != E:
+            raise ValueError(f"W, Omega and adam_state need the same number of rows (W has {E})")
+        if not (isinstance(opt_steps, np.ndarray) and opt_steps.dtype == np.int64 and opt_steps.shape == (E,)
+                and opt_steps.flags.c_contiguous and opt_steps.flags.writeable):
+            raise ValueError(f"opt_steps: a writeable contiguous int64 numpy array [{E}]")
+        missing = [k for k in TSF_TEST_HP if k not in hp]
+        if missing or len(hp) != len(TSF_TEST_HP):
+            raise ValueError(f"hp: a dict of exactly {TSF_TEST_HP}")
+        chp = TsfTestHP(*(float(hp[k]) for k in TSF_TEST_HP))
+        horizon = int(self.episode_len if horizon is None else horizon)
+        ex = None
+        if explore is not None:
+            ex = np.ascontiguousarray(np.asarray(explore, dtype=np.int32))
+            if ex.shape != (E, horizon, 2):
+                raise ValueError(f"explore: an int array [{E}, {horizon}, 2]")
+        n = max(E, 1)
+        ret, loss = np.zeros(n, np.float64), np.zeros((n, 3), np.float64)
+        steps = np.zeros(n, np.int64)
+        acts = np.full((n, max(horizon, 1), 2), -1, np.int64) if want_actions else None
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None  # noqa: E731
+        self._check(self._lib.sfx_runner_tsf_test_phase(
+            self._r, E, horizon, float(test_epsilon), C.byref(chp), W.data_ptr(), int(W.shape[1]), Omega.data_ptr(),
+            int(Omega.shape[1]), adam_state.data_ptr(), int(adam_state.shape[1]),
+            ptr(opt_steps) if E else ptr(np.zeros(1, np.int64)), ptr(ex), ptr(ret), ptr(loss), ptr(steps), ptr(acts)),
+            "sfx_runner_tsf_test_phase")
+        out = (ret[:E], loss[:E], steps[:E])
+        return out + (acts[:E, :horizon],) if want_actions else out
+
     def train(self, tasks, n_samples: int, W, n_test_ev: int = 1000, cycles_per_task: int = 1, **test_kwargs):
         """SFDQN.train's loop (agents/sfdqn.py:102-123) on the runner: for every cycle and every training task
         (``tasks``: the task indices, or their number), ``set_task`` and ``n_samples`` env steps, with a test phase
-        (``test_phase(W, **test_kwargs)``) after each training step t with ``t % n_test_ev == 0`` -- after step 1,
-        step n_test_ev + 1, ...  Returns ``return_data``: per phase the float32 mean of the E returns, as
-        ``torch.mean(torch.Tensor(Rs))`` gives.  All ``cycles_per_task`` cycles run: the reference returns from
-        inside its cycle loop after the first one, which is a bug and is not copied."""
+        (``test_phase(W, **test_kwargs)``; under schedule "tsf" ``tsf_test_phase(W, **test_kwargs)``, the other
+        test-task state -- Omega, adam_state, opt_steps, hp -- among the keywords) after each training step t
+        with ``t % n_test_ev == 0`` -- after step 1, step n_test_ev + 1, ...  Returns ``return_data``: per phase
+        the float32 mean of the E returns, as ``torch.mean(torch.Tensor(Rs))`` gives.  All ``cycles_per_task``
+        cycles run: the reference returns from inside its cycle loop after the first one, which is a
+        bug and is not copied."""
         idx = list(range(tasks)) if isinstance(tasks, int) else [int(t) for t in tasks]
         return_data = []
+        phase = self.tsf_test_phase if self.schedule == "tsf" else self.test_phase
         for _ in range(int(cycles_per_task)):
             for index in idx:
                 self.set_task(index)
@@ -486,7 +560,7 @@ class NativeEnvLoop:
                 for t in test_phase_steps(n_samples, n_test_ev):
                     self.run(t + 1 - done)
                     done = t + 1
-                    Rs = self.test_phase(W, **test_kwargs)[0]
+                    Rs = phase(W, **test_kwargs)[0]
                     return_data.append(torch.mean(torch.Tensor(Rs.tolist())).numpy()[()])
                 self.run(n_samples - done)
         return return_data

@@ -488,6 +488,61 @@ int sfx_runner_test_env(sfx_runner_t r, sfx_env_reset_fn reset_fn, sfx_env_step_
 int sfx_runner_test_phase(sfx_runner_t r, int E, int horizon, float test_epsilon, double lr, double wd, float* W_dev,
                           int w_stride, const int* explore_host, double* returns_host, double* loss_host,
                           long long* steps_host, long long* actions_host);
+/*
+ * The TSF agent's test phase in the runner (the evaluation block of TSFDQN.train,
+ * agents/tsfdqn_sequential.py:363-369 over test_agent :392-433), with the E episodes stepped together.
+ *
+ * sfx_tsf_test_lr_omega: lr of ω's parameter group at scheduler epoch `epoch` -- LambdaLR over
+ *   (1 - decay) ** epoch (:344-348): (float)(lr_omega * pow(1.0 - decay, (double)epoch)).  Host only.
+ *
+ * sfx_runner_tsf_test_phase: [test_agent(task_e, e) for e < E] in lockstep.  Row e owns (caller-owned
+ *   device memory, updated in place exactly as by sfx_tsf_test_updates) its reward weights
+ *   W_dev + e * w_stride [d], its ω Omega_dev + e * o_stride [T], its Adam moments
+ *   adam_state_dev + e * mom_stride [2d + 2T] (m_w, v_w, m_ω, v_ω), and opt_steps_host[e]: the optimizer
+ *   steps (= scheduler epochs) its optimizer took before this phase, advanced on return.  Keep the four
+ *   across phases, as the reference keeps every test task's optim and scheduler for the whole run.
+ *   Step j of row e, in the reference's order: a = explore_host[(e * horizon + j) * 2] when that is
+ *   >= 0, else the greedy action of sfx_tsf_test_actions at s under the current (w, ω); the env steps;
+ *   a1 = explore_host[(e * horizon + j) * 2 + 1] when >= 0, else the greedy action at s1 under the same
+ *   (w, ω); one update_test_reward_mapper step (sfx_tsf_test_updates' arithmetic) with Adam step number
+ *   opt_steps + 1, lr_w, wd_w, wd_omega and lr_ω = sfx_tsf_test_lr_omega(lr_omega, lr_omega_decay,
+ *   opt_steps), ω clamped at 1e-7; then opt_steps += 1 (scheduler.step()).  The next step's greedy action
+ *   is taken at s1 under the updated (w, ω).  A row whose callback reports done still gets that step's a1
+ *   and update and then stops: its W, ω, moments, opt_steps, return, losses and step count no longer
+ *   change.  explore_host NULL: the runner draws the schedule up front from its test-phase stream in the
+ *   reference's order -- task-major, per step for a and then for a1 one uniform and, when it is
+ *   <= test_epsilon, one randrange(A) (:377-381).
+ *   Outputs (host; any may be NULL): returns_host [E] the callbacks' float32 rewards summed in double in
+ *   step order; losses_host [E][3] the double sums of the float32 per-step (loss, l2, l1) in step order
+ *   (accum_loss += loss_t.item() and its two siblings, :410-412); steps_host [E] the steps each row took;
+ *   actions_host [E][horizon][2] the taken (a, a1), -1 after a row ended.
+ *   The env callbacks are sfx_runner_test_env's (the built-in synthetic test tasks when none is set).
+ *   One lockstep step is one cached launch chain on the handle's stream -- intake of the staged
+ *   transitions, one forward for ψ(S), ψ(S1) and ψ⁻(S1) of the E rows, the g features, a row kernel (a1,
+ *   the update, the next greedy action; rows that ended return at once), publication -- issued after
+ *   the host has written the step's staging record; the host's wait is bounded by
+ *   sfx_runner_wait_timeout.  Nothing waits on the device for the host.
+ *   Call between runs: schedule 2 (tsf), unsharded handle, no featurizer, sfx_tsf_setup done with every
+ *   g_t and h loaded, T <= 64, d <= 256, G <= 512, A <= 256, 1 <= E <= min(64, max_batch), horizon >= 1,
+ *   w_stride >= d, o_stride >= T, mom_stride >= 2(d + T), test_epsilon in [0, 1], explore_host entries
+ *   < A, opt_steps_host[e] >= 0 and opt_steps_host[e] + horizon < 2^24 (the step number travels as a
+ *   float), hp and the state pointers non-null; otherwise SFX_E_ARG / SFX_E_STATE naming the limit, with
+ *   nothing launched.  The phase does not touch the heads, w, g_i, h, their Adam state, the target
+ *   counters, the replay ring, the training env, the training random streams or the look-ahead: the
+ *   next sfx_runner_run continues exactly as if the phase had not run.
+ */
+typedef struct sfx_tsf_test_hp {
+  float gamma, beta, lasso;          /* as sfx_tsf_test_updates takes them */
+  double lr_w, wd_w, lr_omega, wd_omega, lr_omega_decay;
+} sfx_tsf_test_hp;
+float sfx_tsf_test_lr_omega(double lr_omega, double decay, long long epoch);
+int sfx_runner_tsf_test_phase(sfx_runner_t r, int E, int horizon, float test_epsilon, const sfx_tsf_test_hp* hp,
+                              float* W_dev, int w_stride, float* Omega_dev, int o_stride,
+                              float* adam_state_dev, int mom_stride,
+                              long long* opt_steps_host,      /* [E] in/out */
+                              const int* explore_host,        /* [E][horizon][2] or NULL */
+                              double* returns_host, double* losses_host /* [E][3] */,
+                              long long* steps_host, long long* actions_host /* [E][horizon][2] or NULL */);
 /* test hooks: keep the input record and (task, have_batch, c, greedy a, taken a, terminal) of
  * the next `capacity` steps */
 int sfx_runner_record(sfx_runner_t r, int capacity);
