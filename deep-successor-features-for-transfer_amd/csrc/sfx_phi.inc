@@ -617,6 +617,70 @@ int phi_rows_impl(sfx_handle* h, const float* S, const int64_t* a, const float* 
   return SFX_OK;
 }
 
+// ---- the learned-φ SF agent's test phase in the runner (sfx_runner_phi_test_phase, sfx_runner.inc) ----
+
+// the handle's part of the phase's preconditions (the E-row calls' own, phi_rows_ok, with the phase's name and
+// status codes; E is checked by the entry point); the phase needs no buffer of the φ state beyond those of the φ
+// setup, so nothing is allocated.  The kernels' shape bounds need no refusal of their own: a φ setup takes
+// 2 n_s + 1 <= 64 only (k_phi_test_intake's LDS holds n_s <= PHI_TEST_NS = 32), and the phase runs under schedule 5
+// only, which sfx_runner_config grants at T <= 64 and A <= 256 (gpi_pick's 256 head / action maxima in LDS).
+int phi_test_phase_ready(sfx_handle* h) {
+  const std::string F = "sfx_runner_phi_test_phase: ";
+  if (h->Tg != h->T) SFX_FAIL(SFX_E_STATE, F + "needs an unsharded handle");
+  if (!h->phi) SFX_FAIL(SFX_E_STATE, F + "needs a φ net (sfx_phi_setup or sfx_phi_setup_dims)");
+  return SFX_OK;
+}
+
+// what a captured lockstep step carries of the φ state: a new φ setup frees them (and clears the graphs)
+void phi_test_phase_ptrs(sfx_handle* h, const void** p) {
+  p[0] = h->phi->p;
+  p[1] = h->phi->acts;
+  p[2] = h->phi->phis;
+}
+
+// One lockstep step's launches on h->stream, a linear chain: intake; φ(S ⊕ a ⊕ S1) of the E rows into the φ
+// state's phis (dead rows ride along: the same launches every step); ψ(S1) of every online head -> R_G, as
+// sfx_phi_test_actions (a role nothing reads afterwards); the row kernel; the publication.
+int phi_test_phase_body(sfx_handle* h, int E, int horizon, float* W, int w_stride, float* Wb, const unsigned char* stage,
+                        unsigned char* blk, float* loss, int64_t* sel, TestResult* res) {
+  const PhiTestDevLayout D = phi_test_dev_layout(h->n_s);
+  PhiTestIntakeArgs I{};
+  I.stage = stage;
+  I.E = E;
+  I.n_s = h->n_s;
+  I.horizon = horizon;
+  I.hdr = reinterpret_cast<PhiTestDevHdr*>(blk + D.hdr);
+  I.live = reinterpret_cast<int*>(blk + D.live);
+  I.a = reinterpret_cast<int64_t*>(blk + D.a);
+  I.r = reinterpret_cast<float*>(blk + D.r);
+  I.S = reinterpret_cast<float*>(blk + D.S);
+  I.S1 = reinterpret_cast<float*>(blk + D.S1);
+  hipLaunchKernelGGL(k_phi_test_intake, dim3(1), dim3(256), 0, h->stream, I);
+  LAUNCHCHK();
+  RC(phi_rows_impl(h, I.S, I.a, I.S1, E, h->phi->phis));
+  RC(run_fwd(h, {{R_G, P_ONLINE, 1, 0, h->T}}, E, I.S1, nullptr));
+  GpiArgs g = gpi_args(R_G, 0, 0, W, nullptr, nullptr, nullptr, nullptr, sel, 0, 1, E);
+  g.w_stride = w_stride;
+  g.sel_stride = 2;
+  PhiTestArgs A = phi_test_args(h);
+  A.w = W;
+  PhiTestRowArgs X{};
+  X.hdr = I.hdr;
+  X.live = I.live;
+  X.r = I.r;
+  X.loss = loss;
+  X.E = E;
+  X.horizon = horizon;
+  X.w_stride = w_stride;
+  launch(h, K_GPI, 4.0 * E * ((double)h->T * h->O + 4.0 * h->d + 5.0), k_phi_test_row, dim3(E), dim3(256), h->G, g, Wb, A,
+         X);
+  LAUNCHCHK();
+  hipLaunchKernelGGL(k_test_publish, dim3(1), dim3(128), 0, h->stream, (const int64_t*)sel, E,
+                     (const long long*)&I.hdr->seq, res);
+  LAUNCHCHK();
+  return SFX_OK;
+}
+
 }  // namespace
 
 extern "C" {

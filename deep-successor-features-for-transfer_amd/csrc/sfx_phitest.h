@@ -545,11 +545,13 @@ __global__ __launch_bounds__(64) void k_phi_test_steps(PhiTestArgs A, const floa
 // SFDQN_PHI.get_test_action's greedy branch for E test tasks (agents/sfdqn_phi.py:223-232 over
 // features/deep_phi.py GPI_w): k_gpi's row with the reward model's bias added AFTER the dot product,
 // q[e,t,a] = fl(ψ_t(S[e])[a,:]·W[e,:] + Wb[e]), then the first-index argmaxes.  One workgroup per row.
-__global__ __launch_bounds__(256) void k_phi_test_act(Geo G, GpiArgs A, const float* Wb) {
+// phi_test_act_row is the whole 256-thread workgroup's body for row b; k_phi_test_act and the native test
+// phase's row kernel (k_phi_test_row, sfx_testphase.h) both call it.
+__device__ __forceinline__ void phi_test_act_row(const Geo& G, const GpiArgs& A, const float* Wb, const int b) {
   __shared__ float s_q[QMAX];
   __shared__ float s_w[DMAX];
   __shared__ float s_mt[256], s_ma[256];
-  const int tid = threadIdx.x, b = blockIdx.x;
+  const int tid = threadIdx.x;
   const int T = G.T, Aa = G.A, d = G.d, O = G.O, NLm = G.lastOff, TA = T * Aa;
   const long long ob = (long long)(A.row0 + b);
   const int lb = A.rowoff + b;
@@ -570,6 +572,10 @@ __global__ __launch_bounds__(256) void k_phi_test_act(Geo G, GpiArgs A, const fl
   }
   __syncthreads();
   gpi_pick(A, s_q, s_mt, s_ma, T, Aa, ob, so, 256);
+}
+
+__global__ __launch_bounds__(256) void k_phi_test_act(Geo G, GpiArgs A, const float* Wb) {
+  phi_test_act_row(G, A, Wb, blockIdx.x);
 }
 
 }  // namespace sfx

@@ -208,6 +208,12 @@ struct sfx_runner {
   uint8_t* ttblk = nullptr;
   float* ttloss = nullptr;
   size_t ttloss_n = 0;
+  // the learned-φ SF agent's phase (sfx_runner_phi_test_phase): its own staging record (PhiTestStageLayout), device
+  // block (PhiTestDevLayout, the sequence word in its header) and [horizon][E] loss block; result and selections shared
+  uint8_t* ptst = nullptr;
+  uint8_t* ptblk = nullptr;
+  float* ptloss = nullptr;
+  size_t ptloss_n = 0;
 
   float uni() { return std::uniform_real_distribution<float>(0.f, 1.f)(rng); }
   // host-written cancel word next to the go word the gates poll (push: device memory through
@@ -223,6 +229,10 @@ int tsf_test_phase_ready(sfx_handle* h, int E);
 int tsf_test_phase_body(sfx_runner* R, int E, int horizon, float* W, int w_stride, float* Om, int o_stride, float* mom,
                         int mom_stride);
 const void* tsf_test_phase_tgf(sfx_handle* h);
+int phi_test_phase_ready(sfx_handle* h);  // sfx_phi.inc
+void phi_test_phase_ptrs(sfx_handle* h, const void** p);
+int phi_test_phase_body(sfx_handle* h, int E, int horizon, float* W, int w_stride, float* Wb, const unsigned char* stage,
+                        unsigned char* blk, float* loss, int64_t* sel, TestResult* res);
 int shard_tsf_buffers(sfx_handle* h);
 
 bool sharded_sched(const sfx_runner* R) { return R->schedule == RUN_SHARD || R->schedule == RUN_SHARD_TSF; }
@@ -1232,7 +1242,9 @@ int sfx_runner_destroy(sfx_runner_t R) {
   if (R->tst) (void)hipHostFree(R->tst);
   if (R->tres) (void)hipHostFree(R->tres);
   if (R->ttst) (void)hipHostFree(R->ttst);
-  for (void* p : {(void*)R->tS, (void*)R->tsel, (void*)R->tdseq, (void*)R->tloss, (void*)R->ttblk, (void*)R->ttloss})
+  if (R->ptst) (void)hipHostFree(R->ptst);
+  for (void* p : {(void*)R->tS, (void*)R->tsel, (void*)R->tdseq, (void*)R->tloss, (void*)R->ttblk, (void*)R->ttloss,
+                  (void*)R->ptblk, (void*)R->ptloss})
     if (p) (void)hipFree(p);
   for (void* p : {(void*)R->drs, (void*)R->drs1, (void*)R->drphi, (void*)R->drr, (void*)R->drg, (void*)R->dra})
     if (p) (void)hipFree(p);
@@ -1930,6 +1942,142 @@ int sfx_runner_tsf_test_phase(sfx_runner_t R, int E, int horizon, float test_eps
                                     adam_state_dev, mom_stride, opt_steps_host, explore_host, returns_host, losses_host,
                                     steps_host, actions_host);
   if (rc) {  // leave nothing of the phase queued: the staging and the caller's blocks are free again on return
+    const std::string e = g_err;
+    (void)stream_drain(h->stream, std::max(30.0, R->wait_bound));
+    g_err = e;
+  }
+  return rc;
+}
+
+// ---- the learned-φ SF agent's test phase (agents/sfdqn_phi.py:211-212 over test_agent :234-261) ----
+
+namespace {
+
+// the φ phase's buffers: allocated here, never inside a capture
+int phi_test_phase_buffers(sfx_runner* R, int E, int horizon) {
+  sfx_handle* h = R->h;
+  RC(test_phase_shared_buffers(R));
+  if (!R->ptst) {
+    const PhiTestStageLayout L = phi_test_stage_layout(h->n_s);
+    if (hipHostMalloc((void**)&R->ptst, L.bytes, hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess)
+      SFX_FAIL(SFX_E_HIP, "sfx_runner_phi_test_phase: hipHostMalloc(staging) failed");
+    std::memset(R->ptst, 0, L.bytes);
+  }
+  if (!R->ptblk) {
+    const PhiTestDevLayout D = phi_test_dev_layout(h->n_s);
+    HIPCHK(hipMalloc((void**)&R->ptblk, D.bytes));
+    HIPCHK(hipMemset(R->ptblk, 0, D.bytes));
+  }
+  const size_t need = (size_t)E * horizon;
+  if (R->ptloss_n < need) {  // a larger block: the graphs keyed on the old one are never replayed again
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (R->ptloss) (void)hipFree(R->ptloss);
+    R->ptloss = nullptr;
+    R->ptloss_n = 0;
+    HIPCHK(hipMalloc((void**)&R->ptloss, sizeof(float) * need));
+    R->ptloss_n = need;
+  }
+  return SFX_OK;
+}
+
+// cached per (E, w_stride, horizon, the caller's W and Wb, the phase's buffers, the φ state's): one graph a phase
+int phi_test_step_launch(sfx_runner* R, int E, int horizon, float* W, int w_stride, float* Wb) {
+  sfx_handle* h = R->h;
+  const void* ps[3];
+  phi_test_phase_ptrs(h, ps);
+  const GraphKey key = make_key(29, {E, w_stride, horizon}, h->mask,
+                                {W, Wb, R->ptst, R->tres, R->ptblk, R->ptloss, R->tsel, ps[0], ps[1], ps[2]});
+  return run_graph(h, key, [&]() -> int {
+    return phi_test_phase_body(h, E, horizon, W, w_stride, Wb, R->ptst, R->ptblk, R->ptloss, R->tsel, R->tres);
+  });
+}
+
+int phi_test_phase_run(sfx_runner* R, int E, int horizon, float test_epsilon, float* W, int w_stride, float* Wb,
+                       const int* explore, double* returns, double* loss, long long* steps, long long* actions) {
+  sfx_handle* h = R->h;
+  std::vector<int> drawn;
+  if (!explore) {
+    drawn.resize((size_t)E * horizon);
+    draw_test_schedule(R->xrng, E, horizon, test_epsilon, h->A, drawn.data());
+    explore = drawn.data();
+  }
+  if (!R->tenv_step)
+    for (int e = (int)R->trng.size(); e < E; ++e) R->trng.emplace_back(test_stream_seed(R->seed, e));
+  RC(phi_test_phase_buffers(R, E, horizon));
+  PhiTestPhaseHost P;
+  std::vector<double> ret_tmp(E);
+  std::vector<long long> steps_tmp(E);
+  P.begin(E, horizon, h->n_s, h->d, R->ptst, explore, returns ? returns : ret_tmp.data(), steps ? steps : steps_tmp.data(),
+          actions);
+  for (int e = 0; e < E; ++e) RC(test_env_reset(R, e, P.s1_row(e)));
+  P.header(++R->tseq, 0, 0);
+  RC(phi_test_step_launch(R, E, horizon, W, w_stride, Wb));
+  for (int j = 0; j < horizon; ++j) {
+    RC(test_wait(R, R->tseq));
+    for (int e = 0; e < E; ++e) {
+      if (!P.is_live(e)) {
+        P.idle(e);
+        continue;
+      }
+      const long long greedy = R->tres->sel[2 * e + 1];
+      if (greedy < 0 || greedy >= h->A) SFX_FAIL(SFX_E_STATE, "sfx_runner_phi_test_phase: corrupt published action");
+      const int a = P.action(e, j, greedy);
+      float r = 0.f;
+      int term = 0;
+      RC(test_env_step(R, e, a, P.s1_row(e), P.phi_row(), &r, &term));  // the callback's φ is not used
+      P.took(e, j, a, r, term);
+    }
+    const bool last = P.end_step() == 0 || j + 1 == horizon;
+    P.header(++R->tseq, j, 1);
+    RC(phi_test_step_launch(R, E, horizon, W, w_stride, Wb));  // the last record is launched like the others
+    if (last) break;
+  }
+  RC(test_wait(R, R->tseq));
+  std::vector<float> lh((size_t)E * horizon);
+  HIPCHK(hipMemcpyAsync(lh.data(), R->ptloss, sizeof(float) * lh.size(), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  if (loss)
+    for (int e = 0; e < E; ++e) {
+      double acc = 0.0;  // accum_loss += loss.item(), in step order
+      for (long long j = 0; j < P.steps[e]; ++j) acc += (double)lh[(size_t)j * E + e];
+      loss[e] = acc;
+    }
+  return SFX_OK;
+}
+
+}  // namespace
+
+int sfx_runner_phi_test_phase(sfx_runner_t R, int E, int horizon, float test_epsilon, float* W_dev, int w_stride,
+                              float* Wb_dev, const int* explore_host, double* returns_host, double* loss_host,
+                              long long* steps_host, long long* actions_host) {
+  const std::string F = "sfx_runner_phi_test_phase: ";
+  if (!R) SFX_FAIL(SFX_E_ARG, F + "null runner");
+  sfx_handle* h = R->h;
+  if (E < 1 || E > PHI_TEST_EMAX || E > h->Mmax)
+    SFX_FAIL(SFX_E_ARG, F + "E = " + std::to_string(E) + " test tasks, needs 1 <= E <= min(" +
+                            std::to_string(PHI_TEST_EMAX) + ", max_batch = " + std::to_string(h->Mmax) + ")");
+  if (horizon < 1) SFX_FAIL(SFX_E_ARG, F + "horizon = " + std::to_string(horizon) + ", needs horizon >= 1");
+  if (!W_dev || !Wb_dev) SFX_FAIL(SFX_E_ARG, F + "W_dev and Wb_dev need to be non-null");
+  if (w_stride < h->d)
+    SFX_FAIL(SFX_E_ARG, F + "w_stride = " + std::to_string(w_stride) + ", needs w_stride >= d = " + std::to_string(h->d));
+  if (!(test_epsilon >= 0.f && test_epsilon <= 1.f)) SFX_FAIL(SFX_E_ARG, F + "test_epsilon needs to be in [0, 1]");
+  if (explore_host)  // checked before the first step: a phase never stops after it has moved an env or a row
+    for (size_t i = 0; i < (size_t)E * horizon; ++i)
+      if (explore_host[i] >= h->A)
+        SFX_FAIL(SFX_E_ARG, F + "explore_host holds an action >= A = " + std::to_string(h->A));
+  if (R->broken) SFX_FAIL(SFX_E_STATE, R->broken_why.c_str());
+  RC(phi_test_phase_ready(h));  // an unsharded handle with a φ net
+  if (R->feat) SFX_FAIL(SFX_E_STATE, F + "a featurizer is set (sfx_runner_featurizer); clear it first");
+  if (R->schedule != RUN_PHI)
+    SFX_FAIL(SFX_E_STATE, F + "the learned-φ SF agent's test phase runs with the phi schedule only, not with schedule " +
+                              std::to_string(R->schedule) + " (" + RUN_NAMES[R->schedule] + ")");
+  RunnerScope scope(h);
+  RC(settle(h));
+  RC(runner_complete(R));
+  if (R->pre_n) SFX_FAIL(SFX_E_STATE, F + "a step is pre-launched");
+  const int rc = phi_test_phase_run(R, E, horizon, test_epsilon, W_dev, w_stride, Wb_dev, explore_host, returns_host,
+                                    loss_host, steps_host, actions_host);
+  if (rc) {  // leave nothing of the phase queued: the staging and the caller's rows are free again on return
     const std::string e = g_err;
     (void)stream_drain(h->stream, std::max(30.0, R->wait_bound));
     g_err = e;

@@ -2,7 +2,8 @@
 // that needs no device: the staging record's layout, the test-phase random streams, the exploration
 // schedule and the per-row bookkeeping of E lockstep episodes (agents/sfdqn.py:139-166).  Plain C++,
 // so tools/hostsan/test_phase_hostsan.cpp drives it under the host sanitizers without a GPU.  The TSF agent's
-// phase (sfx_runner_tsf_test_phase) has its own layout and bookkeeping below (tools/hostsan/tsf_test_phase_hostsan.cpp).
+// phase (sfx_runner_tsf_test_phase) has its own layout and bookkeeping below (tools/hostsan/tsf_test_phase_hostsan.cpp),
+// and so has the learned-φ SF agent's (sfx_runner_phi_test_phase; tools/hostsan/phi_test_phase_hostsan.cpp).
 #pragma once
 #include <stdint.h>
 
@@ -271,6 +272,110 @@ struct TsfTestPhaseHost {
     if (actions) actions[((size_t)e * horizon + j) * 2 + 1] = a1;
   }
   void idle(int e) const { live_w()[e] = 0; }
+  int end_step() {
+    int n = 0;
+    for (int e = 0; e < E; ++e) {
+      if (done[e]) live[e] = 0;
+      n += live[e] ? 1 : 0;
+    }
+    return n;
+  }
+};
+
+// -------------------------------------------------------------------------------------
+// The learned-φ SF agent's test phase (sfx_runner_phi_test_phase; agents/sfdqn_phi.py:234-261): per
+// lockstep step a row chooses a at s, steps its env and takes one update_test_reward_mapper step
+// (:263-305) on its own biased Linear(d, 1) with φ = phi_net(s ⊕ a ⊕ s1), computed on the device: the
+// record carries no φ, and the env callback's φ output goes to a sink nobody reads.
+// -------------------------------------------------------------------------------------
+
+constexpr int PHI_TEST_EMAX = 16;  // test tasks of one phase: the E-row φ kernels' PHIE (sfx_phitest.h)
+constexpr int PHI_TEST_NS = 32;    // n_s of a φ net's handle is at most 31 (2 n_s + 1 <= 64): k_phi_test_intake's LDS
+
+// Staging record of one lockstep step of the φ phase (host-coherent):
+//   TestStageHdr | live[PHI_TEST_EMAX] (int) | r[PHI_TEST_EMAX] | a[PHI_TEST_EMAX] (int: the action
+//   taken at s) | s1 [PHI_TEST_EMAX][n_s]
+// The header's neg_lr / wd are not used (0).  Everything in front of s1 is PHI_TEST_PRE bytes.
+constexpr int PHI_TEST_PRE = (int)sizeof(TestStageHdr) + 3 * 4 * PHI_TEST_EMAX;
+static_assert(PHI_TEST_PRE % 16 == 0, "PHI_TEST_PRE: whole 16-byte words");
+
+struct PhiTestStageLayout {
+  int live, r, a, s1;  // byte offsets, multiples of 16
+  size_t bytes;
+};
+
+inline PhiTestStageLayout phi_test_stage_layout(int n_s) {
+  PhiTestStageLayout L{};
+  const auto up16 = [](size_t n) { return (n + 15) / 16 * 16; };
+  L.live = (int)sizeof(TestStageHdr);
+  L.r = L.live + 4 * PHI_TEST_EMAX;
+  L.a = L.r + 4 * PHI_TEST_EMAX;
+  L.s1 = L.a + 4 * PHI_TEST_EMAX;
+  L.bytes = (size_t)L.s1 + up16(sizeof(float) * PHI_TEST_EMAX * (size_t)n_s);
+  return L;
+}
+
+// Bookkeeping of one φ phase: TestPhaseHost's loop, with the action taken written into the record
+// (the φ net reads it) and no φ row.  The exploration schedule is the SF agent's (draw_test_schedule:
+// agents/sfdqn_phi.py:226-227 draws as agents/sfdqn.py does).
+struct PhiTestPhaseHost {
+  int E = 0, horizon = 0, n_s = 0;
+  PhiTestStageLayout L{};
+  uint8_t* st = nullptr;
+  const int* explore = nullptr;  // [E * horizon]
+  double* ret = nullptr;         // [E]
+  long long* steps = nullptr;    // [E]
+  long long* actions = nullptr;  // [E * horizon] or null
+  std::vector<char> live, done;
+  std::vector<float> phi_sink;   // [d]: where the env callback's φ goes
+
+  int* live_w() const { return reinterpret_cast<int*>(st + L.live); }
+  float* r_w() const { return reinterpret_cast<float*>(st + L.r); }
+  int* a_w() const { return reinterpret_cast<int*>(st + L.a); }
+  float* s1_row(int e) const { return reinterpret_cast<float*>(st + L.s1) + (size_t)e * n_s; }
+  float* phi_row() { return phi_sink.data(); }
+
+  void begin(int E_, int horizon_, int n_s_, int d_, uint8_t* staging, const int* explore_, double* ret_,
+             long long* steps_, long long* actions_) {
+    E = E_, horizon = horizon_, n_s = n_s_;
+    L = phi_test_stage_layout(n_s);
+    st = staging, explore = explore_, ret = ret_, steps = steps_, actions = actions_;
+    live.assign(E, 1);
+    done.assign(E, 0);
+    phi_sink.assign(d_ > 0 ? d_ : 1, 0.f);
+    for (int e = 0; e < PHI_TEST_EMAX; ++e) {
+      live_w()[e] = e < E ? 1 : 0;  // the first record carries every row's s0
+      r_w()[e] = 0.f;
+      a_w()[e] = 0;
+    }
+    for (int e = 0; e < E; ++e) {
+      ret[e] = 0.0;
+      steps[e] = 0;
+    }
+    if (actions)
+      for (size_t i = 0; i < (size_t)E * horizon; ++i) actions[i] = -1;
+  }
+  void header(long long seq, int step, int update) const {
+    TestStageHdr hd{seq, step, update, 0.f, 0.f, 0, 0};
+    std::memcpy(st, &hd, sizeof(hd));
+  }
+  bool is_live(int e) const { return live[e] != 0; }
+  // the action row e takes at step j: the schedule's when it explores, else the published greedy one
+  int action(int e, int j, long long greedy) const {
+    const int x = explore[(size_t)e * horizon + j];
+    return x >= 0 ? x : (int)greedy;
+  }
+  void took(int e, int j, int a, float r, int terminal) {
+    if (actions) actions[(size_t)e * horizon + j] = a;
+    ret[e] += (double)r;  // the callback's float32 reward, added in double
+    steps[e] += 1;
+    live_w()[e] = 1;
+    r_w()[e] = r;
+    a_w()[e] = a;
+    done[e] = terminal ? 1 : 0;
+  }
+  void idle(int e) const { live_w()[e] = 0; }
+  // rows whose callback reported done got this step's update and stop; returns the rows still running
   int end_step() {
     int n = 0;
     for (int e = 0; e < E; ++e) {

@@ -232,4 +232,129 @@ __global__ __launch_bounds__(256) void k_tsf_test_row(TsfTestArgs A0, TsfTestRow
   if (tid == 0) X.sel[2 * e + 1] = best;
 }
 
+// -------------------------------------------------------------------------------------
+// The learned-φ SF agent's test phase (sfx_runner_phi_test_phase): E episodes of
+// agents/sfdqn_phi.py:234-261 in lockstep.  One lockstep step is k_phi_test_intake -> the φ forward of
+// the E rows (phi_rows_impl: φ(S ⊕ a ⊕ S1) into the φ state's phis) -> the ψ forward of every online
+// head on the E S1 rows -> k_phi_test_row -> k_test_publish, a linear chain; the staging record is
+// PhiTestStageLayout's (sfx_test_host.h).
+// -------------------------------------------------------------------------------------
+static_assert(PHI_TEST_EMAX == PHIE, "the φ phase steps as many rows as one launch of the E-row φ kernels takes");
+static_assert(PHI_IN <= 2 * PHI_TEST_NS + 1, "every n_s a φ setup takes (2 n_s + 1 <= PHI_IN) fits k_phi_test_intake's LDS");
+
+// what the intake leaves on the device for the row kernel and the publication
+struct PhiTestDevHdr {
+  long long seq;  // the record's sequence number: k_test_publish's dseq
+  int step, update;
+};
+static_assert(sizeof(PhiTestDevHdr) == 16, "PhiTestDevHdr: one 16-byte word");
+
+// The phase's device block, one allocation: byte offsets of its parts (multiples of 16)
+struct PhiTestDevLayout {
+  int hdr, live, a, r, S, S1;
+  size_t bytes;
+};
+inline PhiTestDevLayout phi_test_dev_layout(int n_s) {
+  PhiTestDevLayout L{};
+  const auto up16 = [](size_t n) { return (n + 15) / 16 * 16; };
+  L.hdr = 0;
+  L.live = (int)sizeof(PhiTestDevHdr);
+  L.a = L.live + 4 * PHI_TEST_EMAX;
+  L.r = L.a + 8 * PHI_TEST_EMAX;
+  L.S = L.r + 4 * PHI_TEST_EMAX;
+  L.S1 = L.S + (int)up16(sizeof(float) * PHI_TEST_EMAX * (size_t)n_s);
+  L.bytes = (size_t)L.S1 + up16(sizeof(float) * PHI_TEST_EMAX * (size_t)n_s);
+  return L;
+}
+
+struct PhiTestIntakeArgs {
+  const unsigned char* stage;  // host-coherent staging record (PhiTestStageLayout)
+  int E, n_s, horizon, pad_;
+  PhiTestDevHdr* hdr;
+  int* live;    // [E]
+  int64_t* a;   // [E] the actions taken at s, as the φ kernels read them
+  float* r;     // [E]
+  float* S;     // [E][n_s]: a live row's previous S1 row
+  float* S1;    // [E][n_s]: its new s1
+};
+
+// (a) of a φ lockstep step, one workgroup.  The whole record (at most PHI_TEST_PRE + 2 KB) comes through
+// LDS in 16-byte words.  For every live row the previous S1 row becomes its S row and the record's s1
+// its S1 row; its action (widened) and r go to the device block, the live mask and the header too.  The
+// phase's first record (update 0) carries the initial states: S = S1 = s0 and a = 0, so the φ forward
+// of that launch reads defined rows.  A row that is not live keeps everything it had.
+__global__ __launch_bounds__(256) void k_phi_test_intake(PhiTestIntakeArgs A) {
+  constexpr int PRE16 = PHI_TEST_PRE / 16;
+  __shared__ __attribute__((aligned(16))) uint4 s_rec[PRE16 + PHI_TEST_EMAX * PHI_TEST_NS / 4];
+  const int tid = threadIdx.x;
+  SFX_CHK(A.E >= 1 && A.E <= PHI_TEST_EMAX && A.n_s <= PHI_TEST_NS, A.E, A.n_s, 0);
+  if (A.E < 1 || A.E > PHI_TEST_EMAX || A.n_s < 1 || A.n_s > PHI_TEST_NS) return;  // refused by the host already
+  const int nrow = A.E * A.n_s;
+  const uint4* src = reinterpret_cast<const uint4*>(A.stage);
+  for (int i = tid; i < PRE16 + (nrow + 3) / 4; i += 256) s_rec[i] = src[i];
+  __syncthreads();
+  const TestStageHdr& H = *reinterpret_cast<const TestStageHdr*>(s_rec);
+  const int* live = reinterpret_cast<const int*>(s_rec) + sizeof(TestStageHdr) / 4;
+  const float* r = reinterpret_cast<const float*>(live + PHI_TEST_EMAX);
+  const int* a = live + 2 * PHI_TEST_EMAX;
+  const float* s1 = reinterpret_cast<const float*>(s_rec + PRE16);
+  const FDiv fn = fdiv(A.n_s);
+  for (int i = tid; i < nrow; i += 256) {
+    const int e = i / fn;
+    SFX_CHK(e >= 0 && e < A.E, e, A.E, i);
+    if (live[e]) {
+      const float v = s1[i];
+      A.S[i] = H.update ? A.S1[i] : v;
+      A.S1[i] = v;
+    }
+  }
+  if (tid < A.E) {
+    A.live[tid] = live[tid];
+    if (live[tid]) {
+      A.a[tid] = H.update ? a[tid] : 0;
+      A.r[tid] = r[tid];
+    }
+  }
+  if (tid == 0) {
+    SFX_CHK(!H.update || (H.step >= 0 && H.step < A.horizon), H.step, A.horizon, H.update);
+    A.hdr->step = H.step;
+    A.hdr->update = H.update;
+    __hip_atomic_store(&A.hdr->seq, H.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
+struct PhiTestRowArgs {
+  const PhiTestDevHdr* hdr;
+  const int* live;  // [E]
+  const float* r;   // [E]
+  float* loss;      // [horizon][E]: the pre-step loss of each step's update
+  int E, horizon, w_stride, pad_;
+};
+
+// (c) of a φ lockstep step, one workgroup per row; a row that is not live returns at once.  When the
+// header asks for an update: one update_test_reward_mapper step on the row's (w, b) with φ_e
+// (phi_test_step_row: k_phi_test_steps' arithmetic), its loss into loss[step][e].  Then, whatever the
+// flag, the biased GPI selection at S1 under the updated (w, b) (phi_test_act_row: k_phi_test_act's
+// arithmetic) into sel[e] = (c, a): the action the row takes next unless it explores.  G / g:
+// sfx_phi_test_actions' arguments (ψ(S1) of the E rows in g.role); A: sfx_phi_test_updates'.
+__global__ __launch_bounds__(256) void k_phi_test_row(Geo G, GpiArgs g, float* Wb, PhiTestArgs A, PhiTestRowArgs X) {
+  const int e = blockIdx.x;
+  SFX_CHK(e < X.E && X.E <= PHI_TEST_EMAX, e, X.E, 0);
+  if (!X.live[e]) return;
+  const int update = X.hdr->update, hstep = X.hdr->step;
+  if (update) {  // the header is the grid's: a uniform branch
+    SFX_CHK(hstep >= 0 && hstep < X.horizon, hstep, X.horizon, e);
+    const int step = hstep >= 0 && hstep < X.horizon ? hstep : 0;
+    A.w += (long long)e * X.w_stride;
+    A.wb = Wb + e;
+    A.phi += (long long)e * A.d;
+    A.r = X.r[e];
+    A.losses = X.loss + (size_t)step * X.E + e;
+    phi_test_step_row(A);
+    __threadfence_block();  // the row's stores of w and b: visible to the whole workgroup
+    __syncthreads();
+  }
+  phi_test_act_row(G, g, Wb, e);
+}
+
 }  // namespace sfx

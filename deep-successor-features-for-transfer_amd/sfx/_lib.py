@@ -163,6 +163,7 @@ SIGNATURES = {
     "sfx_tsf_test_lr_omega": (_F, [_D, _D, C.c_longlong]),
     "sfx_runner_tsf_test_phase": (_I, [_VP, _I, _I, _F, _VP, _VP, _I, _VP, _I, _VP, _I, _VP, _VP, _VP, _VP, _VP,
                                        _VP]),
+    "sfx_runner_phi_test_phase": (_I, [_VP, _I, _I, _F, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP]),
 }
 
 

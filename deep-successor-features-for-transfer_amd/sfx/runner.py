@@ -293,7 +293,9 @@ class NativeEnvLoop:
     ``set_test_env`` / ``test_phase`` step the test tasks of ``test_agent`` in lockstep between runs without
     touching training, and ``train`` is SFDQN.train's loop over both.  Under "tsf" the TSF agent's test phase
     (agents/tsfdqn_sequential.py:392-433) does: ``tsf_test_phase`` steps the test tasks in lockstep, each with its
-    own (w, ω), Adam moments and ω-lr schedule, and ``train`` evaluates with it.
+    own (w, ω), Adam moments and ω-lr schedule, and ``train`` evaluates with it.  Under "phi" the learned-φ SF
+    agent's (agents/sfdqn_phi.py:234-261) does: ``phi_test_phase`` steps the test tasks in lockstep, each with its
+    own biased reward model (W row, Wb entry), and ``train`` evaluates with it (``Wb=...`` among the keywords).
     """
 
     FIELDS =("s", "s1", "phi", "a", "gamma", "snext", "phi1", "r1", "rb")
@@ -445,7 +447,10 @@ class NativeEnvLoop:
             try:
                 ns, ph, rr, tt = env.step(e, a)
                 np.ctypeslib.as_array(s1, shape=(n_s,))[:] = np.asarray(ns, np.float32).reshape(n_s)
-                np.ctypeslib.as_array(phi, shape=(d,))[:] = np.asarray(ph, np.float32).reshape(d)
+                if ph is None and self.schedule == "phi":  # phi_test_phase does not use the env's φ
+                    np.ctypeslib.as_array(phi, shape=(d,))[:] = 0.0
+                else:
+                    np.ctypeslib.as_array(phi, shape=(d,))[:] = np.asarray(ph, np.float32).reshape(d)
                 r[0] = float(rr)
                 term[0] = 1 if tt else 0
                 return 0
@@ -541,18 +546,62 @@ class NativeEnvLoop:
         out = (ret[:E], loss[:E], steps[:E])
         return out + (acts[:E, :horizon],) if want_actions else out
 
+    def phi_test_phase(self, W, Wb, horizon=None, test_epsilon: float = 0.03, explore=None,
+                       want_actions: bool = False):
+        """sfx_runner_phi_test_phase: ``[test_agent(task_e, e) for e in range(E)]`` of agents/sfdqn_phi.py:234-261
+        with the E episodes in lockstep inside the runner (schedule "phi", between runs).  W: a contiguous float32
+        device tensor [E, >= d], row e the weight of test task e's biased Linear(d, 1); Wb: a contiguous float32
+        device tensor of E elements, its bias; both are updated in place (update_test_reward_mapper :263-305, φ
+        from the φ net on the device -- the test env's φ is not used and its ``step`` may return None for it).
+        horizon: steps per episode (default: the loop's episode_len, the reference's agent.T).  explore: None (the
+        runner draws the ε-schedule from its own stream) or an int array [E, horizon] of explored actions < A,
+        -1 = greedy (``draw_test_schedule``: the draw is the SF agent's, :226-227).  Returns numpy ``(returns,
+        loss_sums, steps)`` -- float64 [E], float64 [E], int64 [E] -- and, with want_actions, the taken actions
+        int64 [E, horizon] (-1 once a row ended).  Training state is not touched: the next ``run`` continues as
+        if no phase had run."""
+        C, e = self._C, self.eng
+        if not (isinstance(W, torch.Tensor) and W.dtype == torch.float32 and W.dim() == 2 and W.is_contiguous()
+                and W.device == torch.device(e.device)):
+            raise ValueError(f"W: a contiguous float32 tensor [E, >= d] on {e.device}")
+        E, stride = int(W.shape[0]), int(W.shape[1])
+        if not (isinstance(Wb, torch.Tensor) and Wb.dtype == torch.float32 and Wb.is_contiguous() and Wb.numel() == E
+                and Wb.device == torch.device(e.device)):
+            raise ValueError(f"Wb: a contiguous float32 tensor of E = {E} elements on {e.device}")
+        horizon = int(self.episode_len if horizon is None else horizon)
+        ex = None
+        if explore is not None:
+            ex = np.ascontiguousarray(np.asarray(explore, dtype=np.int32))
+            if ex.shape != (E, horizon):
+                raise ValueError(f"explore: an int array [{E}, {horizon}]")
+            if ex.size and int(ex.max()) >= int(e.A):
+                raise ValueError(f"explore: holds an action >= A = {int(e.A)}")
+        n = max(E, 1)
+        ret, loss = np.zeros(n, np.float64), np.zeros(n, np.float64)
+        steps = np.zeros(n, np.int64)
+        acts = np.full((n, max(horizon, 1)), -1, np.int64) if want_actions else None
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None  # noqa: E731
+        self._check(self._lib.sfx_runner_phi_test_phase(self._r, E, horizon, float(test_epsilon), W.data_ptr(), stride,
+                                                        Wb.data_ptr(), ptr(ex), ptr(ret), ptr(loss), ptr(steps),
+                                                        ptr(acts)), "sfx_runner_phi_test_phase")
+        out = (ret[:E], loss[:E], steps[:E])
+        return out + (acts[:E, :horizon],) if want_actions else out
+
     def train(self, tasks, n_samples: int, W, n_test_ev: int = 1000, cycles_per_task: int = 1, **test_kwargs):
         """SFDQN.train's loop (agents/sfdqn.py:102-123) on the runner: for every cycle and every training task
         (``tasks``: the task indices, or their number), ``set_task`` and ``n_samples`` env steps, with a test phase
         (``test_phase(W, **test_kwargs)``; under schedule "tsf" ``tsf_test_phase(W, **test_kwargs)``, the other
-        test-task state -- Omega, adam_state, opt_steps, hp -- among the keywords) after each training step t
+        test-task state -- Omega, adam_state, opt_steps, hp -- among the keywords; under schedule "phi"
+        ``phi_test_phase(W, **test_kwargs)``, the biases ``Wb`` among the keywords) after each training step t
         with ``t % n_test_ev == 0`` -- after step 1, step n_test_ev + 1, ...  Returns ``return_data``: per phase
         the float32 mean of the E returns, as ``torch.mean(torch.Tensor(Rs))`` gives.  All ``cycles_per_task``
         cycles run: the reference returns from inside its cycle loop after the first one, which is a
         bug and is not copied."""
         idx = list(range(tasks)) if isinstance(tasks, int) else [int(t) for t in tasks]
         return_data = []
-        phase = self.tsf_test_phase if self.schedule == "tsf" else self.test_phase
+        if self.schedule == "phi":
+            phase = self.phi_test_phase
+        else:
+            phase = self.tsf_test_phase if self.schedule == "tsf" else self.test_phase
         for _ in range(int(cycles_per_task)):
             for index in idx:
                 self.set_task(index)

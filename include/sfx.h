@@ -543,6 +543,50 @@ int sfx_runner_tsf_test_phase(sfx_runner_t r, int E, int horizon, float test_eps
                               const int* explore_host,        /* [E][horizon][2] or NULL */
                               double* returns_host, double* losses_host /* [E][3] */,
                               long long* steps_host, long long* actions_host /* [E][horizon][2] or NULL */);
+/*
+ * The learned-φ SF agent's test phase in the runner (the evaluation block of SFDQN_PHI.train,
+ * agents/sfdqn_phi.py:211-212 over test_agent :234-261), with the E episodes stepped together.
+ *
+ * sfx_runner_phi_test_phase: [test_agent(task_e, e) for e < E] in lockstep.  Row e owns (caller-owned
+ *   device memory, updated in place exactly as by sfx_phi_test_updates) its reward model, the biased
+ *   Linear(d, 1) W_dev + e * w_stride [d] with the bias Wb_dev[e].
+ *   Step j of row e: a = explore_host[e * horizon + j] when that is >= 0, else the greedy action of
+ *   sfx_phi_test_actions at s under the current (W[e], Wb[e]) (get_test_action :223-232: GPI_w with
+ *   q = fl(ψ·w + b)); the env steps (the callback's φ output is ignored, as under schedule 5; its r is
+ *   used); one update_test_reward_mapper step (:263-305) on (s, a, r, s1) with sfx_phi_test_update's
+ *   arithmetic -- φ = phi_net(s ⊕ a ⊕ s1), a freshly built Adam at the φ setup's lr.  The next step's
+ *   greedy action is taken at s1 under the updated (W[e], Wb[e]).  A row whose callback reports done
+ *   still gets that step's update and then stops: its W, bias, return, loss sum and step count no longer
+ *   change.  explore_host NULL: the runner draws the schedule up front from its test-phase stream in the
+ *   SF phase's order -- task-major, one uniform per step and, when it is <= test_epsilon, one
+ *   randrange(A) (:226-227).
+ *   Outputs (host; any may be NULL), with sfx_runner_test_phase's meanings: returns_host [E] the
+ *   callbacks' float32 rewards summed in double in step order; loss_host [E] the double sums of the
+ *   float32 pre-step losses (accum_loss += loss.item(), :248); steps_host [E] the steps each row took;
+ *   actions_host [E][horizon] the taken actions, -1 after a row ended.
+ *   The env callbacks are sfx_runner_test_env's (the built-in synthetic test tasks when none is set).
+ *   One lockstep step is one cached launch chain on the handle's stream -- intake of the staged
+ *   transitions, the φ forward of the E rows, the ψ forward of every online head at the E next states,
+ *   a row kernel (the update, then the next greedy action; rows that ended return at once),
+ *   publication -- issued after the host has written the step's staging record; the host's wait is
+ *   bounded by sfx_runner_wait_timeout.  Nothing waits on the device for the host.  A phase uses one
+ *   graph per (E, w_stride, W_dev, Wb_dev, horizon) and slot mask; a second phase with the same
+ *   arguments captures nothing.
+ *   Call between runs: schedule 5 (phi), unsharded handle, a φ net (sfx_phi_setup / sfx_phi_setup_dims),
+ *   no featurizer, 1 <= E <= min(16, max_batch), horizon >= 1, w_stride >= d, test_epsilon in [0, 1],
+ *   explore_host entries < A, W_dev and Wb_dev non-null; otherwise SFX_E_ARG / SFX_E_STATE naming the
+ *   limit, with nothing launched and the runner usable.  The phase writes only the caller's W and Wb,
+ *   its own buffers, the φ net's activations and φ rows (every update recomputes them first) and the
+ *   activation role sfx_phi_test_actions uses, which nothing reads afterwards.  It does not touch the
+ *   heads, the φ net, their Adam state, w, the per-task bias and λ scalars, the target counters, the
+ *   replay ring, the training env, the training random streams or the GPI counters: the next
+ *   sfx_runner_run continues exactly as if the phase had not run.  The TSF-φ agent (schedule 6) has no
+ *   such phase: its Ω is one module every test task's update writes, so its test tasks run in sequence.
+ */
+int sfx_runner_phi_test_phase(sfx_runner_t r, int E, int horizon, float test_epsilon, float* W_dev, int w_stride,
+                              float* Wb_dev, const int* explore_host /* [E][horizon] or NULL */,
+                              double* returns_host, double* loss_host, long long* steps_host,
+                              long long* actions_host /* [E][horizon] or NULL */);
 /* test hooks: keep the input record and (task, have_batch, c, greedy a, taken a, terminal) of
  * the next `capacity` steps */
 int sfx_runner_record(sfx_runner_t r, int capacity);
