@@ -184,36 +184,30 @@ struct sfx_runner {
   std::vector<uint8_t> rec_stage;
   std::vector<long long> rec_meta;  // task, have, c, a_greedy, a_taken, terminal
 
-  // native test phase (sfx_runner_test_env / sfx_runner_test_phase): the test tasks' callbacks (null: the
-  // built-in synthetic test tasks, one generator each in trng), the exploration schedule's own stream,
-  // the host-coherent staging record and result, the device state block, selections, sequence word and
-  // the phase's loss block; allocated by the first phase
+  // native test phases (sfx_runner_test_env / sfx_runner_*test_phase): the test tasks' callbacks (null: the
+  // built-in synthetic test tasks, one generator each in trng), the exploration schedule's own stream, and
+  // what the three kinds of phase share: the host-coherent result, the device selections, the sequence word
+  // (the φ phase keeps its own in its device block's header) and the launch-set counter
   unsigned long long seed = 0;
   sfx_env_reset_fn tenv_reset = nullptr;
   sfx_env_step_fn tenv_step = nullptr;
   void* tenv_ctx = nullptr;
   std::vector<std::mt19937_64> trng;
   std::mt19937_64 xrng;
-  uint8_t* tst = nullptr;
   TestResult* tres = nullptr;
-  float* tS = nullptr;
   int64_t* tsel = nullptr;
   long long* tdseq = nullptr;
-  float* tloss = nullptr;
-  size_t tloss_n = 0;
   long long tseq = 0;
-  // the TSF agent's phase (sfx_runner_tsf_test_phase): its own staging record (TsfTestStageLayout), device
-  // block (TsfTestDevLayout) and [horizon][E][3] loss block; result, selections and sequence word are shared
-  uint8_t* ttst = nullptr;
-  uint8_t* ttblk = nullptr;
-  float* ttloss = nullptr;
-  size_t ttloss_n = 0;
-  // the learned-φ SF agent's phase (sfx_runner_phi_test_phase): its own staging record (PhiTestStageLayout), device
-  // block (PhiTestDevLayout, the sequence word in its header) and [horizon][E] loss block; result and selections shared
-  uint8_t* ptst = nullptr;
-  uint8_t* ptblk = nullptr;
-  float* ptloss = nullptr;
-  size_t ptloss_n = 0;
+  // a kind's own buffers, allocated by its first phase (the step graphs are keyed on their addresses): the
+  // host-coherent staging record (TestStageLayout), the device block (SF: the state rows [TEST_EMAX][n_s]; TSF:
+  // TsfTestDevLayout; φ: PhiTestDevLayout) and the loss block [horizon][E] (TSF: [horizon][E][3])
+  enum { TP_SF = 0, TP_TSF = 1, TP_PHI = 2 };
+  struct TestPhaseBufs {
+    uint8_t* st = nullptr;
+    uint8_t* blk = nullptr;
+    float* loss = nullptr;
+    size_t loss_n = 0;
+  } tp[3];
 
   float uni() { return std::uniform_real_distribution<float>(0.f, 1.f)(rng); }
   // host-written cancel word next to the go word the gates poll (push: device memory through
@@ -1239,13 +1233,14 @@ int sfx_runner_destroy(sfx_runner_t R) {
   if (R->dloss) (void)hipFree(R->dloss);
   if (R->dpush) (void)hipFree(R->dpush);
   if (R->dgo) (void)hipFree(R->dgo);
-  if (R->tst) (void)hipHostFree(R->tst);
   if (R->tres) (void)hipHostFree(R->tres);
-  if (R->ttst) (void)hipHostFree(R->ttst);
-  if (R->ptst) (void)hipHostFree(R->ptst);
-  for (void* p : {(void*)R->tS, (void*)R->tsel, (void*)R->tdseq, (void*)R->tloss, (void*)R->ttblk, (void*)R->ttloss,
-                  (void*)R->ptblk, (void*)R->ptloss})
+  for (void* p : {(void*)R->tsel, (void*)R->tdseq})
     if (p) (void)hipFree(p);
+  for (const sfx_runner::TestPhaseBufs& b : R->tp) {
+    if (b.st) (void)hipHostFree(b.st);
+    if (b.blk) (void)hipFree(b.blk);
+    if (b.loss) (void)hipFree(b.loss);
+  }
   for (void* p : {(void*)R->drs, (void*)R->drs1, (void*)R->drphi, (void*)R->drr, (void*)R->drg, (void*)R->dra})
     if (p) (void)hipFree(p);
   delete R;
@@ -1542,8 +1537,11 @@ int sfx_runner_test_env(sfx_runner_t R, sfx_env_reset_fn reset_fn, sfx_env_step_
 
 namespace {
 
-// what the SF and the TSF phase share: the published result, the device selections and the sequence word
-int test_phase_shared_buffers(sfx_runner* R) {
+using TestPhaseBufs = sfx_runner::TestPhaseBufs;
+
+// A kind's buffers and what the kinds share; allocated here, never inside a capture.  A larger loss block
+// replaces the old one: the graphs keyed on that one are never replayed again.
+int test_phase_buffers(sfx_runner* R, int kind, const std::string& F, size_t st_bytes, size_t blk_bytes, size_t loss_need) {
   if (!R->tres) {
     if (hipHostMalloc((void**)&R->tres, sizeof(TestResult), hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess)
       SFX_FAIL(SFX_E_HIP, "sfx_runner_test_phase: hipHostMalloc(result) failed");
@@ -1557,42 +1555,37 @@ int test_phase_shared_buffers(sfx_runner* R) {
     HIPCHK(hipMalloc((void**)&R->tdseq, 64));
     HIPCHK(hipMemset(R->tdseq, 0, 64));
   }
-  return SFX_OK;
-}
-
-// the phase's buffers: allocated here, never inside a capture
-int test_phase_buffers(sfx_runner* R, int E, int horizon) {
-  sfx_handle* h = R->h;
-  const TestStageLayout L = test_stage_layout(h->n_s, h->d);
-  if (!R->tst) {
-    if (hipHostMalloc((void**)&R->tst, L.bytes, hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess)
-      SFX_FAIL(SFX_E_HIP, "sfx_runner_test_phase: hipHostMalloc(staging) failed");
-    std::memset(R->tst, 0, L.bytes);
+  TestPhaseBufs& b = R->tp[kind];
+  if (!b.st) {
+    if (hipHostMalloc((void**)&b.st, st_bytes, hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess)
+      SFX_FAIL(SFX_E_HIP, F + "hipHostMalloc(staging) failed");
+    std::memset(b.st, 0, st_bytes);
   }
-  RC(test_phase_shared_buffers(R));
-  if (!R->tS) {
-    HIPCHK(hipMalloc((void**)&R->tS, sizeof(float) * TEST_EMAX * h->n_s));
-    HIPCHK(hipMemset(R->tS, 0, sizeof(float) * TEST_EMAX * h->n_s));
+  if (!b.blk) {
+    HIPCHK(hipMalloc((void**)&b.blk, blk_bytes));
+    HIPCHK(hipMemset(b.blk, 0, blk_bytes));
   }
-  const size_t need = (size_t)E * horizon;
-  if (R->tloss_n < need) {  // a larger block: the graphs keyed on the old one are never replayed again
-    if (R->tloss) (void)hipFree(R->tloss);
-    R->tloss = nullptr;
-    R->tloss_n = 0;
-    HIPCHK(hipMalloc((void**)&R->tloss, sizeof(float) * need));
-    R->tloss_n = need;
+  if (b.loss_n < loss_need) {
+    HIPCHK(hipStreamSynchronize(R->h->stream));
+    if (b.loss) (void)hipFree(b.loss);
+    b.loss = nullptr;
+    b.loss_n = 0;
+    HIPCHK(hipMalloc((void**)&b.loss, sizeof(float) * loss_need));
+    b.loss_n = loss_need;
   }
   return SFX_OK;
 }
 
-// One lockstep step's launch set on h->stream: intake; when `full`, the forward of all heads on the
-// E rows chunked by max_batch (sfx_test_actions' launches), the GPI selection with per-row W, and
+// One lockstep step's launch set of the SF phase on h->stream: intake; when `full`, the forward of all heads
+// on the E rows chunked by max_batch (sfx_test_actions' launches), the GPI selection with per-row W, and
 // the publication.  The phase's trailing launch (the last transitions' updates) is the intake alone.
 int test_step_body(sfx_runner* R, int E, int horizon, float* W, int w_stride, bool full) {
   sfx_handle* h = R->h;
+  const TestPhaseBufs& b = R->tp[sfx_runner::TP_SF];
   const TestStageLayout L = test_stage_layout(h->n_s, h->d);
+  float* S = reinterpret_cast<float*>(b.blk);
   TestIntakeArgs A{};
-  A.stage = R->tst;
+  A.stage = b.st;
   A.off_phi = L.phi;
   A.off_s1 = L.s1;
   A.E = E;
@@ -1601,15 +1594,15 @@ int test_step_body(sfx_runner* R, int E, int horizon, float* W, int w_stride, bo
   A.w_stride = w_stride;
   A.horizon = horizon;
   A.W = W;
-  A.S = R->tS;
-  A.loss = R->tloss;
+  A.S = S;
+  A.loss = b.loss;
   A.dseq = R->tdseq;
   hipLaunchKernelGGL(k_test_intake, dim3(1), dim3(256), 0, h->stream, A);
   LAUNCHCHK();
   if (!full) return SFX_OK;
   for (int row0 = 0; row0 < E; row0 += h->Mmax) {
     const int m = E - row0 < h->Mmax ? E - row0 : h->Mmax;
-    RC(run_fwd(h, {{R_G, P_ONLINE, 1, 0, h->T}}, m, R->tS + (size_t)row0 * h->n_s, nullptr));
+    RC(run_fwd(h, {{R_G, P_ONLINE, 1, 0, h->T}}, m, S + (size_t)row0 * h->n_s, nullptr));
     GpiArgs g = gpi_args(R_G, 0, row0, W, nullptr, nullptr, nullptr, nullptr, R->tsel, 0, 1, m);
     g.w_stride = w_stride;
     g.sel_stride = 2;
@@ -1624,9 +1617,35 @@ int test_step_body(sfx_runner* R, int E, int horizon, float* W, int w_stride, bo
 // cached per (E, w_stride, W, horizon's loss block): at most two graphs a phase (full / trailing)
 int test_step_launch(sfx_runner* R, int E, int horizon, float* W, int w_stride, bool full) {
   sfx_handle* h = R->h;
+  const TestPhaseBufs& b = R->tp[sfx_runner::TP_SF];
   const GraphKey key = make_key(27, {E, w_stride, horizon, full ? 1 : 0}, h->mask,
-                                {W, R->tst, R->tres, R->tS, R->tsel, R->tloss, R->tdseq});
+                                {W, b.st, R->tres, b.blk, R->tsel, b.loss, R->tdseq});
   return run_graph(h, key, [&]() -> int { return test_step_body(R, E, horizon, W, w_stride, full); });
+}
+
+// cached per (E, strides, horizon, the caller's blocks, the phase's buffers): one graph a phase
+int tsf_test_step_launch(sfx_runner* R, int E, int horizon, float* W, int w_stride, float* Om, int o_stride, float* mom,
+                         int mom_stride) {
+  sfx_handle* h = R->h;
+  const TestPhaseBufs& b = R->tp[sfx_runner::TP_TSF];
+  const GraphKey key = make_key(28, {E, w_stride, o_stride, mom_stride, horizon}, h->mask,
+                                {W, Om, mom, b.st, R->tres, b.blk, b.loss, R->tsel, R->tdseq, tsf_test_phase_tgf(h)});
+  return run_graph(h, key, [&]() -> int {
+    return tsf_test_phase_body(R, E, horizon, W, w_stride, Om, o_stride, mom, mom_stride);
+  });
+}
+
+// cached per (E, w_stride, horizon, the caller's W and Wb, the phase's buffers, the φ state's): one graph a phase
+int phi_test_step_launch(sfx_runner* R, int E, int horizon, float* W, int w_stride, float* Wb) {
+  sfx_handle* h = R->h;
+  const TestPhaseBufs& b = R->tp[sfx_runner::TP_PHI];
+  const void* ps[3];
+  phi_test_phase_ptrs(h, ps);
+  const GraphKey key =
+      make_key(29, {E, w_stride, horizon}, h->mask, {W, Wb, b.st, R->tres, b.blk, b.loss, R->tsel, ps[0], ps[1], ps[2]});
+  return run_graph(h, key, [&]() -> int {
+    return phi_test_phase_body(h, E, horizon, W, w_stride, Wb, b.st, b.blk, b.loss, R->tsel, R->tres);
+  });
 }
 
 // Wait (bounded by sfx_runner_wait_timeout) for launch set `seq` to publish its selections.
@@ -1676,223 +1695,205 @@ int test_env_step(sfx_runner* R, int e, int a, float* s1, float* phi, float* r, 
   return SFX_OK;
 }
 
-int test_phase_run(sfx_runner* R, int E, int horizon, float test_epsilon, double lr, double wd, float* W, int w_stride,
-                   const int* explore, double* returns, double* loss, long long* steps, long long* actions) {
+// what tells the three kinds of phase apart for lockstep_phase_run
+struct LockstepSpec {
+  int kind;                             // sfx_runner::TP_*
+  std::string F;                        // the entry point's name, in front of its messages
+  TestStageLayout L;                    // the kind's staging record
+  size_t blk_bytes;                     // its device block
+  int draws;                            // schedule entries per step: 1; TSF 2 (a, then a1, which the device reports)
+  int comps;                            // loss components per row-step: 1; TSF 3
+  bool trailing_intake;                 // SF: the last record's launch is the intake alone, which publishes nothing
+  float neg_lr = 0.f, wd = 0.f;         // SF: the header's SGD constants
+  const sfx_tsf_test_hp* hp = nullptr;  // TSF: the phase's hyperparameters
+  long long* opt_steps = nullptr;       // TSF: [E] in/out
+};
+
+// The lockstep loop of every kind: draw the schedule, seed the built-in tasks, reset, launch the first record
+// (every row's s0); then per step wait for the publication, step every live row's env on the published (or
+// scheduled) action, stage the transitions and launch.  launch(full): one step's launch set; full is false only
+// for a trailing intake.  Afterwards the loss block comes back and is summed per row in step order.
+int lockstep_phase_run(sfx_runner* R, const LockstepSpec& sp, int E, int horizon, float test_epsilon, const int* explore,
+                       double* returns, double* loss, long long* steps, long long* actions,
+                       const std::function<int(bool full)>& launch) {
   sfx_handle* h = R->h;
   std::vector<int> drawn;
   if (!explore) {
-    drawn.resize((size_t)E * horizon);
-    draw_test_schedule(R->xrng, E, horizon, test_epsilon, h->A, drawn.data());
+    drawn.resize((size_t)E * horizon * sp.draws);
+    draw_test_schedule(R->xrng, E, horizon * sp.draws, test_epsilon, h->A, drawn.data());
     explore = drawn.data();
   }
   if (!R->tenv_step)
     for (int e = (int)R->trng.size(); e < E; ++e) R->trng.emplace_back(test_stream_seed(R->seed, e));
-  RC(test_phase_buffers(R, E, horizon));
+  RC(test_phase_buffers(R, sp.kind, sp.F, sp.L.bytes, sp.blk_bytes, (size_t)E * horizon * sp.comps));
+  const TestPhaseBufs& b = R->tp[sp.kind];
   TestPhaseHost P;
   std::vector<double> ret_tmp(E);
   std::vector<long long> steps_tmp(E);
-  P.begin(E, horizon, h->n_s, h->d, R->tst, explore, returns ? returns : ret_tmp.data(), steps ? steps : steps_tmp.data(),
-          actions);
-  const float neg_lr = (float)(-lr), wdf = (float)wd;
-  for (int e = 0; e < E; ++e) RC(test_env_reset(R, e, P.s1_row(e)));
-  P.header(++R->tseq, 0, 0, neg_lr, wdf);
-  RC(test_step_launch(R, E, horizon, W, w_stride, true));
-  for (int j = 0; j < horizon; ++j) {
-    RC(test_wait(R, R->tseq));
-    for (int e = 0; e < E; ++e) {
-      if (!P.is_live(e)) {
-        P.idle(e);
-        continue;
-      }
-      const long long greedy = R->tres->sel[2 * e + 1];
-      if (greedy < 0 || greedy >= h->A) SFX_FAIL(SFX_E_STATE, "sfx_runner_test_phase: corrupt published action");
-      const int a = P.action(e, j, greedy);
-      float r = 0.f;
-      int term = 0;
-      RC(test_env_step(R, e, a, P.s1_row(e), P.phi_row(e), &r, &term));
-      P.took(e, j, a, r, term);
-    }
-    const bool last = P.end_step() == 0 || j + 1 == horizon;
-    P.header(++R->tseq, j, 1, neg_lr, wdf);
-    RC(test_step_launch(R, E, horizon, W, w_stride, !last));
-    if (last) break;
+  P.begin(sp.L, sp.draws, E, horizon, h->n_s, h->d, b.st, explore, returns ? returns : ret_tmp.data(),
+          steps ? steps : steps_tmp.data(), actions);
+  if (sp.hp) {
+    TsfTestRowHP rhp;
+    rhp.lr_w = (float)sp.hp->lr_w;
+    rhp.wd_w = (float)sp.hp->wd_w;
+    rhp.wd_omega = (float)sp.hp->wd_omega;
+    rhp.lr_omega = sp.hp->lr_omega;
+    rhp.lr_omega_decay = sp.hp->lr_omega_decay;
+    P.begin_tsf(rhp, sp.hp->gamma, sp.hp->beta, sp.hp->lasso, sp.opt_steps);
   }
-  std::vector<float> lh((size_t)E * horizon);
-  HIPCHK(hipMemcpyAsync(lh.data(), R->tloss, sizeof(float) * lh.size(), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  if (loss)
-    for (int e = 0; e < E; ++e) {
-      double acc = 0.0;  // accum_loss += loss.item(), in step order
-      for (long long j = 0; j < P.steps[e]; ++j) acc += (double)lh[(size_t)j * E + e];
-      loss[e] = acc;
-    }
-  return SFX_OK;
-}
-
-}  // namespace
-
-int sfx_runner_test_phase(sfx_runner_t R, int E, int horizon, float test_epsilon, double lr, double wd, float* W_dev,
-                          int w_stride, const int* explore_host, double* returns_host, double* loss_host,
-                          long long* steps_host, long long* actions_host) {
-  if (!R) SFX_FAIL(SFX_E_ARG, "sfx_runner_test_phase: null runner");
-  sfx_handle* h = R->h;
-  if (E < 1 || E > TEST_EMAX)
-    SFX_FAIL(SFX_E_ARG, "sfx_runner_test_phase: E = " + std::to_string(E) + " test tasks, needs 1 <= E <= " +
-                            std::to_string(TEST_EMAX));
-  if (horizon < 1) SFX_FAIL(SFX_E_ARG, "sfx_runner_test_phase: horizon = " + std::to_string(horizon) + ", needs horizon >= 1");
-  if (!W_dev) SFX_FAIL(SFX_E_ARG, "sfx_runner_test_phase: W_dev is null");
-  if (w_stride < h->d)
-    SFX_FAIL(SFX_E_ARG, "sfx_runner_test_phase: w_stride = " + std::to_string(w_stride) + ", needs w_stride >= d = " +
-                            std::to_string(h->d));
-  if (!(test_epsilon >= 0.f && test_epsilon <= 1.f))
-    SFX_FAIL(SFX_E_ARG, "sfx_runner_test_phase: test_epsilon needs to be in [0, 1]");
-  if (explore_host)  // checked before the first step: a phase never stops after it has moved an env or a W row
-    for (size_t i = 0; i < (size_t)E * horizon; ++i)
-      if (explore_host[i] >= h->A)
-        SFX_FAIL(SFX_E_ARG, "sfx_runner_test_phase: explore_host holds an action >= A = " + std::to_string(h->A));
-  if (R->broken) SFX_FAIL(SFX_E_STATE, R->broken_why.c_str());
-  if (h->Tg != h->T) SFX_FAIL(SFX_E_STATE, "sfx_runner_test_phase: needs an unsharded handle");
-  if (R->schedule != RUN_ALL && R->schedule != RUN_ACTIVE)
-    SFX_FAIL(SFX_E_STATE, std::string("sfx_runner_test_phase: the SF agent's test phase runs with the all and active "
-                                      "schedules only, not with schedule ") +
-                              std::to_string(R->schedule) + " (" + RUN_NAMES[R->schedule] + ")");
-  if (R->feat)
-    SFX_FAIL(SFX_E_STATE, "sfx_runner_test_phase: a featurizer is set (sfx_runner_featurizer); clear it first");
-  RunnerScope scope(h);
-  RC(settle(h));
-  RC(runner_complete(R));
-  if (R->pre_n) SFX_FAIL(SFX_E_STATE, "sfx_runner_test_phase: a step is pre-launched");
-  const int rc = test_phase_run(R, E, horizon, test_epsilon, lr, wd, W_dev, w_stride, explore_host, returns_host,
-                                loss_host, steps_host, actions_host);
-  if (rc) {  // leave nothing of the phase queued: the staging and the caller's W are free again on return
-    const std::string e = g_err;
-    (void)stream_drain(h->stream, std::max(30.0, R->wait_bound));
-    g_err = e;
-  }
-  return rc;
-}
-
-// ---- the TSF agent's test phase (agents/tsfdqn_sequential.py:363-369 over test_agent :392-433) ----
-
-namespace {
-
-// the TSF phase's buffers: allocated here, never inside a capture
-int tsf_test_phase_buffers(sfx_runner* R, int E, int horizon) {
-  sfx_handle* h = R->h;
-  RC(test_phase_shared_buffers(R));
-  if (!R->ttst) {
-    const TsfTestStageLayout L = tsf_test_stage_layout(h->n_s, h->d);
-    if (hipHostMalloc((void**)&R->ttst, L.bytes, hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess)
-      SFX_FAIL(SFX_E_HIP, "sfx_runner_tsf_test_phase: hipHostMalloc(staging) failed");
-    std::memset(R->ttst, 0, L.bytes);
-  }
-  if (!R->ttblk) {
-    const TsfTestDevLayout D = tsf_test_dev_layout(h->n_s, h->d);
-    HIPCHK(hipMalloc((void**)&R->ttblk, D.bytes));
-    HIPCHK(hipMemset(R->ttblk, 0, D.bytes));
-  }
-  const size_t need = (size_t)E * horizon * 3;
-  if (R->ttloss_n < need) {  // a larger block: the graphs keyed on the old one are never replayed again
-    HIPCHK(hipStreamSynchronize(h->stream));
-    if (R->ttloss) (void)hipFree(R->ttloss);
-    R->ttloss = nullptr;
-    R->ttloss_n = 0;
-    HIPCHK(hipMalloc((void**)&R->ttloss, sizeof(float) * need));
-    R->ttloss_n = need;
-  }
-  return SFX_OK;
-}
-
-// cached per (E, strides, horizon, the caller's blocks, the phase's buffers): one graph a phase
-int tsf_test_step_launch(sfx_runner* R, int E, int horizon, float* W, int w_stride, float* Om, int o_stride, float* mom,
-                         int mom_stride) {
-  sfx_handle* h = R->h;
-  const GraphKey key = make_key(28, {E, w_stride, o_stride, mom_stride, horizon}, h->mask,
-                                {W, Om, mom, R->ttst, R->tres, R->ttblk, R->ttloss, R->tsel, R->tdseq, tsf_test_phase_tgf(h)});
-  return run_graph(h, key, [&]() -> int {
-    return tsf_test_phase_body(R, E, horizon, W, w_stride, Om, o_stride, mom, mom_stride);
-  });
-}
-
-int tsf_test_phase_run(sfx_runner* R, int E, int horizon, float test_epsilon, const sfx_tsf_test_hp& hp, float* W,
-                       int w_stride, float* Om, int o_stride, float* mom, int mom_stride, long long* opt_steps,
-                       const int* explore, double* returns, double* losses, long long* steps, long long* actions) {
-  sfx_handle* h = R->h;
-  std::vector<int> drawn;
-  if (!explore) {
-    drawn.resize((size_t)E * horizon * 2);
-    draw_tsf_test_schedule(R->xrng, E, horizon, test_epsilon, h->A, drawn.data());
-    explore = drawn.data();
-  }
-  if (!R->tenv_step)
-    for (int e = (int)R->trng.size(); e < E; ++e) R->trng.emplace_back(test_stream_seed(R->seed, e));
-  RC(tsf_test_phase_buffers(R, E, horizon));
-  TsfTestPhaseHost P;
-  std::vector<double> ret_tmp(E);
-  std::vector<long long> steps_tmp(E);
-  TsfTestRowHP rhp;
-  rhp.lr_w = (float)hp.lr_w;
-  rhp.wd_w = (float)hp.wd_w;
-  rhp.wd_omega = (float)hp.wd_omega;
-  rhp.lr_omega = hp.lr_omega;
-  rhp.lr_omega_decay = hp.lr_omega_decay;
-  P.begin(E, horizon, h->n_s, h->d, R->ttst, explore, rhp, hp.gamma, hp.beta, hp.lasso, opt_steps,
-          returns ? returns : ret_tmp.data(), steps ? steps : steps_tmp.data(), actions);
-  const auto launch_step = [&]() -> int {
-    return tsf_test_step_launch(R, E, horizon, W, w_stride, Om, o_stride, mom, mom_stride);
+  // 0 <= v < A, or the phase stops: a published selection the host is about to act on or to report
+  const auto published = [&](int e, int k, long long* v) -> int {
+    *v = R->tres->sel[2 * e + k];
+    if (*v < 0 || *v >= h->A) SFX_FAIL(SFX_E_STATE, sp.F + "corrupt published action");
+    return SFX_OK;
   };
-  // the a1 the device chose for the rows of the record just published (step j)
+  // TSF: the a1 the device chose for the rows of the record just published (step j)
   const auto collect_a1 = [&](int j) -> int {
     for (int e = 0; e < E; ++e) {
       if (!P.in_record(e)) continue;
-      const long long a1 = R->tres->sel[2 * e];
-      if (a1 < 0 || a1 >= h->A) SFX_FAIL(SFX_E_STATE, "sfx_runner_tsf_test_phase: corrupt published action");
+      long long a1;
+      RC(published(e, 0, &a1));
       P.took_a1(e, j, a1);
     }
     return SFX_OK;
   };
   for (int e = 0; e < E; ++e) RC(test_env_reset(R, e, P.s1_row(e)));
-  P.header(++R->tseq, 0, 0);
-  RC(launch_step());
+  P.header(++R->tseq, 0, 0, sp.neg_lr, sp.wd);
+  RC(launch(true));
   int last_j = -1;
   for (int j = 0; j < horizon; ++j) {
     RC(test_wait(R, R->tseq));
-    if (j > 0) RC(collect_a1(j - 1));
+    if (sp.draws == 2 && j > 0) RC(collect_a1(j - 1));
     for (int e = 0; e < E; ++e) {
       if (!P.is_live(e)) {
         P.idle(e);
         continue;
       }
-      const long long greedy = R->tres->sel[2 * e + 1];
-      if (greedy < 0 || greedy >= h->A) SFX_FAIL(SFX_E_STATE, "sfx_runner_tsf_test_phase: corrupt published action");
+      long long greedy;
+      RC(published(e, 1, &greedy));
       const int a = P.action(e, j, greedy);
       float r = 0.f;
       int term = 0;
-      RC(test_env_step(R, e, a, P.s1_row(e), P.phi_row(e), &r, &term));
+      RC(test_env_step(R, e, a, P.s1_row(e), P.phi_row(e), &r, &term));  // no φ column: the callback's φ is not used
       P.took(e, j, a, r, term);
     }
     const bool last = P.end_step() == 0 || j + 1 == horizon;
-    P.header(++R->tseq, j, 1);
-    RC(launch_step());
+    P.header(++R->tseq, j, 1, sp.neg_lr, sp.wd);
+    RC(launch(!(last && sp.trailing_intake)));
     last_j = j;
     if (last) break;
   }
-  RC(test_wait(R, R->tseq));
-  RC(collect_a1(last_j));
-  std::vector<float> lh((size_t)E * horizon * 3);
-  HIPCHK(hipMemcpyAsync(lh.data(), R->ttloss, sizeof(float) * lh.size(), hipMemcpyDeviceToHost, h->stream));
+  if (!sp.trailing_intake) {  // the last record was launched like the others; a trailing intake is not waited for
+    RC(test_wait(R, R->tseq));
+    if (sp.draws == 2) RC(collect_a1(last_j));
+  }
+  std::vector<float> lh((size_t)E * horizon * sp.comps);
+  HIPCHK(hipMemcpyAsync(lh.data(), b.loss, sizeof(float) * lh.size(), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
-  if (losses)
+  if (loss)
     for (int e = 0; e < E; ++e)
-      for (int c = 0; c < 3; ++c) {
-        double acc = 0.0;  // accum_loss += loss_t.item() and its siblings, in step order
-        for (long long j = 0; j < P.steps[e]; ++j) acc += (double)lh[((size_t)j * E + e) * 3 + c];
-        losses[(size_t)e * 3 + c] = acc;
+      for (int c = 0; c < sp.comps; ++c) {
+        double acc = 0.0;  // accum_loss += loss.item() (and its siblings), in step order
+        for (long long j = 0; j < P.steps[e]; ++j) acc += (double)lh[((size_t)j * E + e) * sp.comps + c];
+        loss[(size_t)e * sp.comps + c] = acc;
       }
   return SFX_OK;
 }
 
+// ---- the entry points' refusals; each entry point calls them in its own order ----
+
+// the caller has found E out of range; max_batch is named when it bounds E as well
+int refuse_E(const std::string& F, int E, int emax, int max_batch) {
+  const std::string lim = max_batch > 0 ? "min(" + std::to_string(emax) + ", max_batch = " + std::to_string(max_batch) + ")"
+                                        : std::to_string(emax);
+  SFX_FAIL(SFX_E_ARG, F + "E = " + std::to_string(E) + " test tasks, needs 1 <= E <= " + lim);
+}
+int need_horizon(const std::string& F, int horizon) {
+  if (horizon < 1) SFX_FAIL(SFX_E_ARG, F + "horizon = " + std::to_string(horizon) + ", needs horizon >= 1");
+  return SFX_OK;
+}
+int need_stride(const std::string& F, const char* name, int stride, const char* of, int least) {
+  if (stride < least)
+    SFX_FAIL(SFX_E_ARG, F + name + " = " + std::to_string(stride) + ", needs " + name + " >= " + of + " = " +
+                            std::to_string(least));
+  return SFX_OK;
+}
+int need_epsilon(const std::string& F, float test_epsilon) {
+  if (!(test_epsilon >= 0.f && test_epsilon <= 1.f)) SFX_FAIL(SFX_E_ARG, F + "test_epsilon needs to be in [0, 1]");
+  return SFX_OK;
+}
+// checked before the first step: a phase never stops after it has moved an env or a row
+int need_explore(const std::string& F, const int* explore, size_t n, int A) {
+  if (explore)
+    for (size_t i = 0; i < n; ++i)
+      if (explore[i] >= A) SFX_FAIL(SFX_E_ARG, F + "explore_host holds an action >= A = " + std::to_string(A));
+  return SFX_OK;
+}
+int need_sound(sfx_runner* R) {
+  if (R->broken) SFX_FAIL(SFX_E_STATE, R->broken_why.c_str());
+  return SFX_OK;
+}
+int need_no_featurizer(const std::string& F, sfx_runner* R) {
+  if (R->feat) SFX_FAIL(SFX_E_STATE, F + "a featurizer is set (sfx_runner_featurizer); clear it first");
+  return SFX_OK;
+}
+// whose: "the SF agent's test phase runs with the all and active schedules only"
+int need_schedule(const std::string& F, sfx_runner* R, bool ok, const char* whose) {
+  if (!ok)
+    SFX_FAIL(SFX_E_STATE,
+             F + whose + ", not with schedule " + std::to_string(R->schedule) + " (" + RUN_NAMES[R->schedule] + ")");
+  return SFX_OK;
+}
+// after the refusals, inside the entry point's RunnerScope: nothing of a training step in flight or pre-launched
+int phase_prologue(const std::string& F, sfx_runner* R) {
+  RC(settle(R->h));
+  RC(runner_complete(R));
+  if (R->pre_n) SFX_FAIL(SFX_E_STATE, F + "a step is pre-launched");
+  return SFX_OK;
+}
+// a failed phase leaves nothing queued: the staging and the caller's rows are free again on return
+int phase_drained(sfx_runner* R, int rc) {
+  if (rc) {
+    const std::string e = g_err;
+    (void)stream_drain(R->h->stream, std::max(30.0, R->wait_bound));
+    g_err = e;
+  }
+  return rc;
+}
+
 }  // namespace
+
+// ---- the SF agent's test phase (agents/sfdqn.py:105-120 over test_agent :139-166) ----
+
+int sfx_runner_test_phase(sfx_runner_t R, int E, int horizon, float test_epsilon, double lr, double wd, float* W_dev,
+                          int w_stride, const int* explore_host, double* returns_host, double* loss_host,
+                          long long* steps_host, long long* actions_host) {
+  const std::string F = "sfx_runner_test_phase: ";
+  if (!R) SFX_FAIL(SFX_E_ARG, F + "null runner");
+  sfx_handle* h = R->h;
+  if (E < 1 || E > TEST_EMAX) return refuse_E(F, E, TEST_EMAX, 0);
+  RC(need_horizon(F, horizon));
+  if (!W_dev) SFX_FAIL(SFX_E_ARG, F + "W_dev is null");
+  RC(need_stride(F, "w_stride", w_stride, "d", h->d));
+  RC(need_epsilon(F, test_epsilon));
+  RC(need_explore(F, explore_host, (size_t)E * horizon, h->A));
+  RC(need_sound(R));
+  if (h->Tg != h->T) SFX_FAIL(SFX_E_STATE, F + "needs an unsharded handle");
+  RC(need_schedule(F, R, R->schedule == RUN_ALL || R->schedule == RUN_ACTIVE,
+                   "the SF agent's test phase runs with the all and active schedules only"));
+  RC(need_no_featurizer(F, R));
+  RunnerScope scope(h);
+  RC(phase_prologue(F, R));
+  LockstepSpec sp{sfx_runner::TP_SF, F, test_stage_layout(h->n_s, h->d), sizeof(float) * TEST_EMAX * h->n_s, 1, 1, true};
+  sp.neg_lr = (float)(-lr);
+  sp.wd = (float)wd;
+  return phase_drained(R, lockstep_phase_run(R, sp, E, horizon, test_epsilon, explore_host, returns_host, loss_host,
+                                             steps_host, actions_host, [&](bool full) -> int {
+                                               return test_step_launch(R, E, horizon, W_dev, w_stride, full);
+                                             }));
+}
+
+// ---- the TSF agent's test phase (agents/tsfdqn_sequential.py:363-369 over test_agent :392-433) ----
 
 float sfx_tsf_test_lr_omega(double lr_omega, double decay, long long epoch) {
   return tsf_test_lr_omega(lr_omega, decay, epoch);
@@ -1905,147 +1906,38 @@ int sfx_runner_tsf_test_phase(sfx_runner_t R, int E, int horizon, float test_eps
   const std::string F = "sfx_runner_tsf_test_phase: ";
   if (!R) SFX_FAIL(SFX_E_ARG, F + "null runner");
   sfx_handle* h = R->h;
-  if (E < 1 || E > TEST_EMAX)
-    SFX_FAIL(SFX_E_ARG, F + "E = " + std::to_string(E) + " test tasks, needs 1 <= E <= min(" + std::to_string(TEST_EMAX) +
-                            ", max_batch = " + std::to_string(h->Mmax) + ")");
+  if (E < 1 || E > TEST_EMAX) return refuse_E(F, E, TEST_EMAX, h->Mmax);  // E <= max_batch: tsf_test_phase_ready
   if (!hp || !W_dev || !Omega_dev || !adam_state_dev || !opt_steps_host)
     SFX_FAIL(SFX_E_ARG, F + "hp, W_dev, Omega_dev, adam_state_dev and opt_steps_host need to be non-null");
-  if (horizon < 1) SFX_FAIL(SFX_E_ARG, F + "horizon = " + std::to_string(horizon) + ", needs horizon >= 1");
-  if (w_stride < h->d)
-    SFX_FAIL(SFX_E_ARG, F + "w_stride = " + std::to_string(w_stride) + ", needs w_stride >= d = " + std::to_string(h->d));
-  if (o_stride < h->T)
-    SFX_FAIL(SFX_E_ARG, F + "o_stride = " + std::to_string(o_stride) + ", needs o_stride >= T = " + std::to_string(h->T));
-  if (mom_stride < 2 * (h->d + h->T))
-    SFX_FAIL(SFX_E_ARG, F + "mom_stride = " + std::to_string(mom_stride) + ", needs mom_stride >= 2(d + T) = " +
-                            std::to_string(2 * (h->d + h->T)));
-  if (!(test_epsilon >= 0.f && test_epsilon <= 1.f)) SFX_FAIL(SFX_E_ARG, F + "test_epsilon needs to be in [0, 1]");
+  RC(need_horizon(F, horizon));
+  RC(need_stride(F, "w_stride", w_stride, "d", h->d));
+  RC(need_stride(F, "o_stride", o_stride, "T", h->T));
+  RC(need_stride(F, "mom_stride", mom_stride, "2(d + T)", 2 * (h->d + h->T)));
+  RC(need_epsilon(F, test_epsilon));
   for (int e = 0; e < E; ++e)
     if (opt_steps_host[e] < 0 || opt_steps_host[e] + horizon >= (1LL << 24))
       SFX_FAIL(SFX_E_ARG, F + "opt_steps_host[" + std::to_string(e) + "] = " + std::to_string(opt_steps_host[e]) +
                               ", needs opt_steps >= 0 and opt_steps + horizon < 2^24");
-  if (explore_host)  // checked before the first step: a phase never stops after it has moved an env or a row
-    for (size_t i = 0; i < (size_t)E * horizon * 2; ++i)
-      if (explore_host[i] >= h->A)
-        SFX_FAIL(SFX_E_ARG, F + "explore_host holds an action >= A = " + std::to_string(h->A));
-  if (R->broken) SFX_FAIL(SFX_E_STATE, R->broken_why.c_str());
+  RC(need_explore(F, explore_host, (size_t)E * horizon * 2, h->A));
+  RC(need_sound(R));
   if (!h->tsf) SFX_FAIL(SFX_E_STATE, F + "call sfx_tsf_setup first (and load every g_t and h)");
-  if (R->schedule != RUN_TSF)
-    SFX_FAIL(SFX_E_STATE, F + "the TSF agent's test phase runs with the tsf schedule only, not with schedule " +
-                              std::to_string(R->schedule) + " (" + RUN_NAMES[R->schedule] + ")");
-  if (R->feat) SFX_FAIL(SFX_E_STATE, F + "a featurizer is set (sfx_runner_featurizer); clear it first");
+  RC(need_schedule(F, R, R->schedule == RUN_TSF, "the TSF agent's test phase runs with the tsf schedule only"));
+  RC(need_no_featurizer(F, R));
   RunnerScope scope(h);
-  RC(settle(h));
-  RC(runner_complete(R));
-  if (R->pre_n) SFX_FAIL(SFX_E_STATE, F + "a step is pre-launched");
+  RC(phase_prologue(F, R));
   RC(tsf_test_phase_ready(h, E));
-  const int rc = tsf_test_phase_run(R, E, horizon, test_epsilon, *hp, W_dev, w_stride, Omega_dev, o_stride,
-                                    adam_state_dev, mom_stride, opt_steps_host, explore_host, returns_host, losses_host,
-                                    steps_host, actions_host);
-  if (rc) {  // leave nothing of the phase queued: the staging and the caller's blocks are free again on return
-    const std::string e = g_err;
-    (void)stream_drain(h->stream, std::max(30.0, R->wait_bound));
-    g_err = e;
-  }
-  return rc;
+  LockstepSpec sp{sfx_runner::TP_TSF, F, tsf_test_stage_layout(h->n_s, h->d), tsf_test_dev_layout(h->n_s, h->d).bytes, 2, 3,
+                  false};
+  sp.hp = hp;
+  sp.opt_steps = opt_steps_host;
+  return phase_drained(R, lockstep_phase_run(R, sp, E, horizon, test_epsilon, explore_host, returns_host, losses_host,
+                                             steps_host, actions_host, [&](bool) -> int {
+                                               return tsf_test_step_launch(R, E, horizon, W_dev, w_stride, Omega_dev,
+                                                                           o_stride, adam_state_dev, mom_stride);
+                                             }));
 }
 
 // ---- the learned-φ SF agent's test phase (agents/sfdqn_phi.py:211-212 over test_agent :234-261) ----
-
-namespace {
-
-// the φ phase's buffers: allocated here, never inside a capture
-int phi_test_phase_buffers(sfx_runner* R, int E, int horizon) {
-  sfx_handle* h = R->h;
-  RC(test_phase_shared_buffers(R));
-  if (!R->ptst) {
-    const PhiTestStageLayout L = phi_test_stage_layout(h->n_s);
-    if (hipHostMalloc((void**)&R->ptst, L.bytes, hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess)
-      SFX_FAIL(SFX_E_HIP, "sfx_runner_phi_test_phase: hipHostMalloc(staging) failed");
-    std::memset(R->ptst, 0, L.bytes);
-  }
-  if (!R->ptblk) {
-    const PhiTestDevLayout D = phi_test_dev_layout(h->n_s);
-    HIPCHK(hipMalloc((void**)&R->ptblk, D.bytes));
-    HIPCHK(hipMemset(R->ptblk, 0, D.bytes));
-  }
-  const size_t need = (size_t)E * horizon;
-  if (R->ptloss_n < need) {  // a larger block: the graphs keyed on the old one are never replayed again
-    HIPCHK(hipStreamSynchronize(h->stream));
-    if (R->ptloss) (void)hipFree(R->ptloss);
-    R->ptloss = nullptr;
-    R->ptloss_n = 0;
-    HIPCHK(hipMalloc((void**)&R->ptloss, sizeof(float) * need));
-    R->ptloss_n = need;
-  }
-  return SFX_OK;
-}
-
-// cached per (E, w_stride, horizon, the caller's W and Wb, the phase's buffers, the φ state's): one graph a phase
-int phi_test_step_launch(sfx_runner* R, int E, int horizon, float* W, int w_stride, float* Wb) {
-  sfx_handle* h = R->h;
-  const void* ps[3];
-  phi_test_phase_ptrs(h, ps);
-  const GraphKey key = make_key(29, {E, w_stride, horizon}, h->mask,
-                                {W, Wb, R->ptst, R->tres, R->ptblk, R->ptloss, R->tsel, ps[0], ps[1], ps[2]});
-  return run_graph(h, key, [&]() -> int {
-    return phi_test_phase_body(h, E, horizon, W, w_stride, Wb, R->ptst, R->ptblk, R->ptloss, R->tsel, R->tres);
-  });
-}
-
-int phi_test_phase_run(sfx_runner* R, int E, int horizon, float test_epsilon, float* W, int w_stride, float* Wb,
-                       const int* explore, double* returns, double* loss, long long* steps, long long* actions) {
-  sfx_handle* h = R->h;
-  std::vector<int> drawn;
-  if (!explore) {
-    drawn.resize((size_t)E * horizon);
-    draw_test_schedule(R->xrng, E, horizon, test_epsilon, h->A, drawn.data());
-    explore = drawn.data();
-  }
-  if (!R->tenv_step)
-    for (int e = (int)R->trng.size(); e < E; ++e) R->trng.emplace_back(test_stream_seed(R->seed, e));
-  RC(phi_test_phase_buffers(R, E, horizon));
-  PhiTestPhaseHost P;
-  std::vector<double> ret_tmp(E);
-  std::vector<long long> steps_tmp(E);
-  P.begin(E, horizon, h->n_s, h->d, R->ptst, explore, returns ? returns : ret_tmp.data(), steps ? steps : steps_tmp.data(),
-          actions);
-  for (int e = 0; e < E; ++e) RC(test_env_reset(R, e, P.s1_row(e)));
-  P.header(++R->tseq, 0, 0);
-  RC(phi_test_step_launch(R, E, horizon, W, w_stride, Wb));
-  for (int j = 0; j < horizon; ++j) {
-    RC(test_wait(R, R->tseq));
-    for (int e = 0; e < E; ++e) {
-      if (!P.is_live(e)) {
-        P.idle(e);
-        continue;
-      }
-      const long long greedy = R->tres->sel[2 * e + 1];
-      if (greedy < 0 || greedy >= h->A) SFX_FAIL(SFX_E_STATE, "sfx_runner_phi_test_phase: corrupt published action");
-      const int a = P.action(e, j, greedy);
-      float r = 0.f;
-      int term = 0;
-      RC(test_env_step(R, e, a, P.s1_row(e), P.phi_row(), &r, &term));  // the callback's φ is not used
-      P.took(e, j, a, r, term);
-    }
-    const bool last = P.end_step() == 0 || j + 1 == horizon;
-    P.header(++R->tseq, j, 1);
-    RC(phi_test_step_launch(R, E, horizon, W, w_stride, Wb));  // the last record is launched like the others
-    if (last) break;
-  }
-  RC(test_wait(R, R->tseq));
-  std::vector<float> lh((size_t)E * horizon);
-  HIPCHK(hipMemcpyAsync(lh.data(), R->ptloss, sizeof(float) * lh.size(), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  if (loss)
-    for (int e = 0; e < E; ++e) {
-      double acc = 0.0;  // accum_loss += loss.item(), in step order
-      for (long long j = 0; j < P.steps[e]; ++j) acc += (double)lh[(size_t)j * E + e];
-      loss[e] = acc;
-    }
-  return SFX_OK;
-}
-
-}  // namespace
 
 int sfx_runner_phi_test_phase(sfx_runner_t R, int E, int horizon, float test_epsilon, float* W_dev, int w_stride,
                               float* Wb_dev, const int* explore_host, double* returns_host, double* loss_host,
@@ -2053,36 +1945,24 @@ int sfx_runner_phi_test_phase(sfx_runner_t R, int E, int horizon, float test_eps
   const std::string F = "sfx_runner_phi_test_phase: ";
   if (!R) SFX_FAIL(SFX_E_ARG, F + "null runner");
   sfx_handle* h = R->h;
-  if (E < 1 || E > PHI_TEST_EMAX || E > h->Mmax)
-    SFX_FAIL(SFX_E_ARG, F + "E = " + std::to_string(E) + " test tasks, needs 1 <= E <= min(" +
-                            std::to_string(PHI_TEST_EMAX) + ", max_batch = " + std::to_string(h->Mmax) + ")");
-  if (horizon < 1) SFX_FAIL(SFX_E_ARG, F + "horizon = " + std::to_string(horizon) + ", needs horizon >= 1");
+  if (E < 1 || E > PHI_TEST_EMAX || E > h->Mmax) return refuse_E(F, E, PHI_TEST_EMAX, h->Mmax);
+  RC(need_horizon(F, horizon));
   if (!W_dev || !Wb_dev) SFX_FAIL(SFX_E_ARG, F + "W_dev and Wb_dev need to be non-null");
-  if (w_stride < h->d)
-    SFX_FAIL(SFX_E_ARG, F + "w_stride = " + std::to_string(w_stride) + ", needs w_stride >= d = " + std::to_string(h->d));
-  if (!(test_epsilon >= 0.f && test_epsilon <= 1.f)) SFX_FAIL(SFX_E_ARG, F + "test_epsilon needs to be in [0, 1]");
-  if (explore_host)  // checked before the first step: a phase never stops after it has moved an env or a row
-    for (size_t i = 0; i < (size_t)E * horizon; ++i)
-      if (explore_host[i] >= h->A)
-        SFX_FAIL(SFX_E_ARG, F + "explore_host holds an action >= A = " + std::to_string(h->A));
-  if (R->broken) SFX_FAIL(SFX_E_STATE, R->broken_why.c_str());
+  RC(need_stride(F, "w_stride", w_stride, "d", h->d));
+  RC(need_epsilon(F, test_epsilon));
+  RC(need_explore(F, explore_host, (size_t)E * horizon, h->A));
+  RC(need_sound(R));
   RC(phi_test_phase_ready(h));  // an unsharded handle with a φ net
-  if (R->feat) SFX_FAIL(SFX_E_STATE, F + "a featurizer is set (sfx_runner_featurizer); clear it first");
-  if (R->schedule != RUN_PHI)
-    SFX_FAIL(SFX_E_STATE, F + "the learned-φ SF agent's test phase runs with the phi schedule only, not with schedule " +
-                              std::to_string(R->schedule) + " (" + RUN_NAMES[R->schedule] + ")");
+  RC(need_no_featurizer(F, R));
+  RC(need_schedule(F, R, R->schedule == RUN_PHI, "the learned-φ SF agent's test phase runs with the phi schedule only"));
   RunnerScope scope(h);
-  RC(settle(h));
-  RC(runner_complete(R));
-  if (R->pre_n) SFX_FAIL(SFX_E_STATE, F + "a step is pre-launched");
-  const int rc = phi_test_phase_run(R, E, horizon, test_epsilon, W_dev, w_stride, Wb_dev, explore_host, returns_host,
-                                    loss_host, steps_host, actions_host);
-  if (rc) {  // leave nothing of the phase queued: the staging and the caller's rows are free again on return
-    const std::string e = g_err;
-    (void)stream_drain(h->stream, std::max(30.0, R->wait_bound));
-    g_err = e;
-  }
-  return rc;
+  RC(phase_prologue(F, R));
+  const LockstepSpec sp{sfx_runner::TP_PHI, F, phi_test_stage_layout(h->n_s), phi_test_dev_layout(h->n_s).bytes, 1, 1,
+                        false};
+  return phase_drained(R, lockstep_phase_run(R, sp, E, horizon, test_epsilon, explore_host, returns_host, loss_host,
+                                             steps_host, actions_host, [&](bool) -> int {
+                                               return phi_test_step_launch(R, E, horizon, W_dev, w_stride, Wb_dev);
+                                             }));
 }
 
 int sfx_runner_action(sfx_runner_t R, int64_t* out_host) {

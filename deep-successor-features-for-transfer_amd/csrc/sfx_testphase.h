@@ -84,7 +84,7 @@ __global__ __launch_bounds__(128) void k_test_publish(const int64_t* sel, int E,
 // The TSF agent's test phase (sfx_runner_tsf_test_phase): E episodes of
 // agents/tsfdqn_sequential.py:392-433 in lockstep.  One lockstep step is k_tsf_test_intake -> one ψ
 // forward of the E rows (ψ(S), ψ(S1) online, ψ⁻(S1)) -> k_tsf_test_g -> k_tsf_test_row ->
-// k_test_publish, a linear chain; the staging record is TsfTestStageLayout's (sfx_test_host.h).
+// k_test_publish, a linear chain; the staging record is tsf_test_stage_layout's (sfx_test_host.h).
 // -------------------------------------------------------------------------------------
 
 // what the intake leaves on the device for the row kernel
@@ -115,7 +115,7 @@ inline TsfTestDevLayout tsf_test_dev_layout(int n_s, int d) {
 }
 
 struct TsfTestIntakeArgs {
-  const unsigned char* stage;  // host-coherent staging record (TsfTestStageLayout)
+  const unsigned char* stage;  // host-coherent staging record (tsf_test_stage_layout)
   int off_phi, off_s1;         // byte offsets of φ and s1 in it (multiples of 16)
   int E, d, n_s, horizon;
   TsfTestDevHdr* hdr;
@@ -237,7 +237,7 @@ __global__ __launch_bounds__(256) void k_tsf_test_row(TsfTestArgs A0, TsfTestRow
 // agents/sfdqn_phi.py:234-261 in lockstep.  One lockstep step is k_phi_test_intake -> the φ forward of
 // the E rows (phi_rows_impl: φ(S ⊕ a ⊕ S1) into the φ state's phis) -> the ψ forward of every online
 // head on the E S1 rows -> k_phi_test_row -> k_test_publish, a linear chain; the staging record is
-// PhiTestStageLayout's (sfx_test_host.h).
+// phi_test_stage_layout's (sfx_test_host.h).
 // -------------------------------------------------------------------------------------
 static_assert(PHI_TEST_EMAX == PHIE, "the φ phase steps as many rows as one launch of the E-row φ kernels takes");
 static_assert(PHI_IN <= 2 * PHI_TEST_NS + 1, "every n_s a φ setup takes (2 n_s + 1 <= PHI_IN) fits k_phi_test_intake's LDS");
@@ -268,7 +268,7 @@ inline PhiTestDevLayout phi_test_dev_layout(int n_s) {
 }
 
 struct PhiTestIntakeArgs {
-  const unsigned char* stage;  // host-coherent staging record (PhiTestStageLayout)
+  const unsigned char* stage;  // host-coherent staging record (phi_test_stage_layout)
   int E, n_s, horizon, pad_;
   PhiTestDevHdr* hdr;
   int* live;    // [E]

@@ -699,11 +699,12 @@ int tsf_test_phase_body(sfx_runner* R, int E, int horizon, float* W, int w_strid
                         int mom_stride) {
   sfx_handle* h = R->h;
   sfx_tsf_state* ts = h->tsf;
-  const TsfTestStageLayout L = tsf_test_stage_layout(h->n_s, h->d);
+  const sfx_runner::TestPhaseBufs& tb = R->tp[sfx_runner::TP_TSF];
+  const TestStageLayout L = tsf_test_stage_layout(h->n_s, h->d);
   const TsfTestDevLayout D = tsf_test_dev_layout(h->n_s, h->d);
-  uint8_t* blk = R->ttblk;
+  uint8_t* blk = tb.blk;
   TsfTestIntakeArgs I{};
-  I.stage = R->ttst;
+  I.stage = tb.st;
   I.off_phi = L.phi;
   I.off_s1 = L.s1;
   I.E = E;
@@ -747,7 +748,7 @@ int tsf_test_phase_body(sfx_runner* R, int E, int horizon, float* W, int w_strid
   X.live = I.live;
   X.a1x = I.a1x;
   X.psi_s1 = h->act + (size_t)R_V * h->T * h->actSize;
-  X.loss = R->ttloss;
+  X.loss = tb.loss;
   X.sel = R->tsel;
   X.E = E;
   X.horizon = horizon;

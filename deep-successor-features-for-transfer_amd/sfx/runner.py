@@ -97,6 +97,36 @@ def test_phase_steps(n_samples: int, n_test_ev: int) -> list:
 test_phase_steps.__test__ = False  # a helper, not a pytest case
 
 
+# ---- what NativeEnvLoop's three test-phase wrappers share ----
+
+def _is_f32_on(t, device, dim=None) -> bool:
+    """t is a contiguous float32 tensor on ``device`` (of ``dim`` dimensions when given)."""
+    return (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and (dim is None or t.dim() == dim)
+            and t.is_contiguous() and t.device == torch.device(device))
+
+
+def _explore_array(explore, shape):
+    """The caller's exploration schedule as a contiguous int32 array of ``shape``, or None."""
+    if explore is None:
+        return None
+    ex = np.ascontiguousarray(np.asarray(explore, dtype=np.int32))
+    if ex.shape != shape:
+        raise ValueError(f"explore: an int array [{', '.join(str(n) for n in shape)}]")
+    return ex
+
+
+def _lockstep_call(C, check, fn, what, head, explore, E, horizon, want_actions, comps=(), draws=()):
+    """``fn(*head, explore, returns, loss sums, steps, actions)`` with fresh outputs (at least one row and one step,
+    so that a refused E = 0 or horizon = 0 still hands over valid pointers), sliced to E rows and horizon steps."""
+    n = max(E, 1)
+    ret, loss, steps = np.zeros(n, np.float64), np.zeros((n,) + comps, np.float64), np.zeros(n, np.int64)
+    acts = np.full((n, max(horizon, 1)) + draws, -1, np.int64) if want_actions else None
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None  # noqa: E731
+    check(fn(*head, ptr(explore), ptr(ret), ptr(loss), ptr(steps), ptr(acts)), what)
+    out = (ret[:E], loss[:E], steps[:E])
+    return out + (acts[:E, :horizon],) if want_actions else out
+
+
 class Staging:
     """One pinned host buffer + one device buffer with typed views at fixed offsets."""
 
@@ -474,26 +504,13 @@ class NativeEnvLoop:
         float64 [E], int64 [E] -- and, with want_actions, the taken actions int64 [E, horizon] (-1 once a row
         ended).  Training state is not touched: the next ``run`` continues as if no phase had run."""
         C, e = self._C, self.eng
-        if not (isinstance(W, torch.Tensor) and W.dtype == torch.float32 and W.dim() == 2 and W.is_contiguous()
-                and W.device == torch.device(e.device)):
+        if not _is_f32_on(W, e.device, dim=2):
             raise ValueError(f"W: a contiguous float32 tensor [E, >= d] on {e.device}")
         E, stride = int(W.shape[0]), int(W.shape[1])
         horizon = int(self.episode_len if horizon is None else horizon)
-        ex = None
-        if explore is not None:
-            ex = np.ascontiguousarray(np.asarray(explore, dtype=np.int32))
-            if ex.shape != (E, horizon):
-                raise ValueError(f"explore: an int array [{E}, {horizon}]")
-        n = max(E, 1)
-        ret, loss = np.zeros(n, np.float64), np.zeros(n, np.float64)
-        steps = np.zeros(n, np.int64)
-        acts = np.full((n, max(horizon, 1)), -1, np.int64) if want_actions else None
-        ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None  # noqa: E731
-        self._check(self._lib.sfx_runner_test_phase(self._r, E, horizon, float(test_epsilon), float(lr), float(wd),
-                                                    W.data_ptr(), stride, ptr(ex), ptr(ret), ptr(loss), ptr(steps),
-                                                    ptr(acts)), "sfx_runner_test_phase")
-        out = (ret[:E], loss[:E], steps[:E])
-        return out + (acts[:E, :horizon],) if want_actions else out
+        head = (self._r, E, horizon, float(test_epsilon), float(lr), float(wd), W.data_ptr(), stride)
+        return _lockstep_call(C, self._check, self._lib.sfx_runner_test_phase, "sfx_runner_test_phase", head,
+                              _explore_array(explore, (E, horizon)), E, horizon, want_actions)
 
     def tsf_test_phase(self, W, Omega, adam_state, opt_steps, hp, horizon=None, test_epsilon: float = 0.03,
                        explore=None, want_actions: bool = False):
@@ -514,8 +531,7 @@ class NativeEnvLoop:
 
         C, e = self._C, self.eng
         for name, t in (("W", W), ("Omega", Omega), ("adam_state", adam_state)):
-            if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.dim() == 2 and t.is_contiguous()
-                    and t.device == torch.device(e.device)):
+            if not _is_f32_on(t, e.device, dim=2):
                 raise ValueError(f"{name}: a contiguous float32 tensor [E, ...] on {e.device}")
         E = int(W.shape[0])
         if int(Omega.shape[0]) != E or int(adam_state.shape[0]) != E:
@@ -528,23 +544,11 @@ class NativeEnvLoop:
             raise ValueError(f"hp: a dict of exactly {TSF_TEST_HP}")
         chp = TsfTestHP(*(float(hp[k]) for k in TSF_TEST_HP))
         horizon = int(self.episode_len if horizon is None else horizon)
-        ex = None
-        if explore is not None:
-            ex = np.ascontiguousarray(np.asarray(explore, dtype=np.int32))
-            if ex.shape != (E, horizon, 2):
-                raise ValueError(f"explore: an int array [{E}, {horizon}, 2]")
-        n = max(E, 1)
-        ret, loss = np.zeros(n, np.float64), np.zeros((n, 3), np.float64)
-        steps = np.zeros(n, np.int64)
-        acts = np.full((n, max(horizon, 1), 2), -1, np.int64) if want_actions else None
-        ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None  # noqa: E731
-        self._check(self._lib.sfx_runner_tsf_test_phase(
-            self._r, E, horizon, float(test_epsilon), C.byref(chp), W.data_ptr(), int(W.shape[1]), Omega.data_ptr(),
-            int(Omega.shape[1]), adam_state.data_ptr(), int(adam_state.shape[1]),
-            ptr(opt_steps) if E else ptr(np.zeros(1, np.int64)), ptr(ex), ptr(ret), ptr(loss), ptr(steps), ptr(acts)),
-            "sfx_runner_tsf_test_phase")
-        out = (ret[:E], loss[:E], steps[:E])
-        return out + (acts[:E, :horizon],) if want_actions else out
+        opt = opt_steps if E else np.zeros(1, np.int64)
+        head = (self._r, E, horizon, float(test_epsilon), C.byref(chp), W.data_ptr(), int(W.shape[1]), Omega.data_ptr(),
+                int(Omega.shape[1]), adam_state.data_ptr(), int(adam_state.shape[1]), opt.ctypes.data_as(C.c_void_p))
+        return _lockstep_call(C, self._check, self._lib.sfx_runner_tsf_test_phase, "sfx_runner_tsf_test_phase", head,
+                              _explore_array(explore, (E, horizon, 2)), E, horizon, want_actions, (3,), (2,))
 
     def phi_test_phase(self, W, Wb, horizon=None, test_epsilon: float = 0.03, explore=None,
                        want_actions: bool = False):
@@ -560,31 +564,18 @@ class NativeEnvLoop:
         int64 [E, horizon] (-1 once a row ended).  Training state is not touched: the next ``run`` continues as
         if no phase had run."""
         C, e = self._C, self.eng
-        if not (isinstance(W, torch.Tensor) and W.dtype == torch.float32 and W.dim() == 2 and W.is_contiguous()
-                and W.device == torch.device(e.device)):
+        if not _is_f32_on(W, e.device, dim=2):
             raise ValueError(f"W: a contiguous float32 tensor [E, >= d] on {e.device}")
         E, stride = int(W.shape[0]), int(W.shape[1])
-        if not (isinstance(Wb, torch.Tensor) and Wb.dtype == torch.float32 and Wb.is_contiguous() and Wb.numel() == E
-                and Wb.device == torch.device(e.device)):
+        if not (_is_f32_on(Wb, e.device) and Wb.numel() == E):
             raise ValueError(f"Wb: a contiguous float32 tensor of E = {E} elements on {e.device}")
         horizon = int(self.episode_len if horizon is None else horizon)
-        ex = None
-        if explore is not None:
-            ex = np.ascontiguousarray(np.asarray(explore, dtype=np.int32))
-            if ex.shape != (E, horizon):
-                raise ValueError(f"explore: an int array [{E}, {horizon}]")
-            if ex.size and int(ex.max()) >= int(e.A):
-                raise ValueError(f"explore: holds an action >= A = {int(e.A)}")
-        n = max(E, 1)
-        ret, loss = np.zeros(n, np.float64), np.zeros(n, np.float64)
-        steps = np.zeros(n, np.int64)
-        acts = np.full((n, max(horizon, 1)), -1, np.int64) if want_actions else None
-        ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None  # noqa: E731
-        self._check(self._lib.sfx_runner_phi_test_phase(self._r, E, horizon, float(test_epsilon), W.data_ptr(), stride,
-                                                        Wb.data_ptr(), ptr(ex), ptr(ret), ptr(loss), ptr(steps),
-                                                        ptr(acts)), "sfx_runner_phi_test_phase")
-        out = (ret[:E], loss[:E], steps[:E])
-        return out + (acts[:E, :horizon],) if want_actions else out
+        ex = _explore_array(explore, (E, horizon))
+        if ex is not None and ex.size and int(ex.max()) >= int(e.A):
+            raise ValueError(f"explore: holds an action >= A = {int(e.A)}")
+        head = (self._r, E, horizon, float(test_epsilon), W.data_ptr(), stride, Wb.data_ptr())
+        return _lockstep_call(C, self._check, self._lib.sfx_runner_phi_test_phase, "sfx_runner_phi_test_phase", head,
+                              ex, E, horizon, want_actions)
 
     def train(self, tasks, n_samples: int, W, n_test_ev: int = 1000, cycles_per_task: int = 1, **test_kwargs):
         """SFDQN.train's loop (agents/sfdqn.py:102-123) on the runner: for every cycle and every training task
