@@ -238,12 +238,7 @@ struct sfx_handle {
   int *tsx = nullptr, *tsz = nullptr;
   int *qh = nullptr, *qhs = nullptr;  // local heads' own maxima terms (FwdArgs::qh), qhs inside qh's block
   bool shard_qa = true;  // SFX_SHARD_QA=0: maxima by separate k_qmax launches
-  struct ShardPending {
-    bool active = false;
-    int B = 0;
-    const float *S = nullptr, *S1 = nullptr, *phi = nullptr, *gamma = nullptr, *s_next = nullptr;
-    const int64_t* a = nullptr;
-  } spend;
+  Pending spend;  // the step begun by sfx_shard_begin (per-call protocol), until sfx_shard_finish
 
   float *online = nullptr, *target = nullptr, *am = nullptr, *av = nullptr;
   float *w = nullptr, *wm = nullptr, *wv = nullptr;
@@ -887,6 +882,13 @@ int run_gpi(sfx_handle* h, const GpiArgs& A) {
   return SFX_OK;
 }
 
+// a runner step's result (verdict flag, selection `sel`) to the host, as a launch of its own
+int run_publish(sfx_handle* h, const int64_t* sel, const SelPub& pub) {
+  hipLaunchKernelGGL(k_publish, dim3(1), dim3(64), 0, h->stream, sel, pub.flag, pub.res, pub.dctr, pub.cancel, pub.nonfin);
+  LAUNCHCHK();
+  return SFX_OK;
+}
+
 int run_ver(sfx_handle* h, int M, int npol, bool sel, int post, const GpiArgs& g, const int64_t* spec,
             bool post_host = false) {
   VerArgs V{};
@@ -1026,73 +1028,79 @@ constexpr int POST_ROLE = R_V;
 // next actions of speculative round r (two buffers: round r reads round r-1's while it writes)
 inline int64_t* spec_buf(sfx_handle* h, int r) { return h->spec_next + (size_t)(r & 1) * h->T * MMAX; }
 
-// One speculative round r of the all-task update: every policy takes its GPI next actions
-// with heads t < i seen through role `guess` (round 0: the pre-step heads), every head
-// updates from its read slot into its write slot, the post-update forward of S1 (++ s_next)
-// lands in POST_ROLE.  Only a final round runs k_ver (flag the first policy whose actions
-// were wrong; action selection): an earlier round's verdict would be overwritten unread.
-int launch_round(sfx_handle* h, const sfx_handle::Pending& p, int r, bool final) {
-  const int T = h->T, B = p.B;
-  const int guess = r == 0 ? R_S1 : POST_ROLE, out = POST_ROLE;
-  const float* wsel = h->w + (size_t)p.task * h->dpad;
-  TdgSpec td;
-  td.use_gpi = p.use_gpi;
-  td.guess = guess;
+// What every speculative round r shares (the all-task round below; the sharded rounds of
+// sfx_shard.inc): the backward + Adam of every local head from the TD target that `td` describes
+// (a / gamma filled here), then the post-update forward of S1 (++ the selection row v_xn, or null)
+// into POST_ROLE -- riding from layer 1 on when layer 0 fits the last backward launch (*v0; `vx`: the
+// caller's extras of that forward), else as a plain forward of S1 alone.
+// skip_fwd: the post-update forward of a head that repeats the round before is skipped with it.
+// may_ahead: a final round (device or host) also forwards the next step's minibatch (p.ax) into the
+// other copy of the minibatch roles; the first round that does (the last device round) computes
+// them for every head, skipped or not -- later host rounds skip them with the rest of a head.
+// (Forwarding them in round 0 instead, so that an all-skip round 1 leaves its forwards empty,
+// measured 9 % slower: DESIGN.md §8.)
+int round_body(sfx_handle* h, const sfx_handle::Pending& p, int r, bool final, TdgSpec& td, FwdExtra vx,
+               const float* v_xn, bool skip_fwd, bool may_ahead, float* losses, bool* v0) {
+  const int T = h->T, B = p.B, out = POST_ROLE;
   td.a = p.a;
   td.gamma = p.gamma;
-  td.next = spec_buf(h, r);
-  td.next_stride = MMAX;
-  td.flag = &h->dout->flag;
-  td.prev = r > 0 ? spec_buf(h, r - 1) : nullptr;
-  td.skip = h->skip_rounds;
   BwdExtra bx;
   bx.inc_step = r == 0 ? 1 : 0;  // later rounds redo the same optimizer step
   bool armed = false;
-  bx.skip_fwd = true;  // one role for every round (POST_ROLE)
+  bx.skip_fwd = skip_fwd;
   bx.skip_armed = &armed;
-  // the s_next row rides along in every round that a later round may skip heads after: a skipped
-  // head's row must already be in the role when the final round's selection reads it
-  const bool want_sel = p.sel && (final || bx.skip_fwd);
-  bx.fuse_v0 = can_fuse_v0(h, B + 1);
+  bx.fuse_v0 = *v0 = can_fuse_v0(h, B + 1);
   bx.vRole = out;
   bx.v_x = p.S1;
-  bx.v_xn = want_sel ? p.s_next : nullptr;
-  const int vM = B + (want_sel ? 1 : 0);
-  // look-ahead: the final round (device or host) also forwards the next step's minibatch into the
-  // other copy of the minibatch roles; the first round that does (the last device round) computes
-  // them for every head, skipped or not -- later host rounds skip them with the rest of a head.
-  // (Forwarding them in round 0 instead, so that an all-skip round 1 leaves its forwards empty,
-  // measured 9 % slower: DESIGN.md §8.)
-  const bool ahead = final && p.ax && p.aM > 0 && bx.fuse_v0 && can_fuse_ahead(h, vM, p.aM);
+  bx.v_xn = v_xn;
+  const int vM = B + (v_xn ? 1 : 0);
+  const bool ahead = may_ahead && final && p.ax && p.aM > 0 && bx.fuse_v0 && can_fuse_ahead(h, vM, p.aM);
   const int a_noskip = ahead && r <= h->spec_rounds - 1 ? 1 : 0;
   if (ahead) {
     bx.ax = p.ax;
     bx.aM = p.aM;
     bx.a_noskip = a_noskip;
   }
-  RC(run_bwd(h, 0, T, B, p.S, p.phi, nullptr, p.losses, td, bx));
-  if (bx.fuse_v0) {
-    FwdExtra vx;
-    vx.l0 = 1;
-    vx.skip = armed && r > 0 && bx.skip_fwd ? h->skip : nullptr;
-    if (ahead)
-      RC(run_fwd(h, {{out, P_NEW, 0, 0, T, vM, 0}, {R_NS, P_NEW, 0, 0, T, p.aM, a_noskip},
-                     {R_NS1, P_NEW, 0, 0, T, p.aM, a_noskip}, {R_NS1T, P_TARGET, 0, 0, T, p.aM, a_noskip}},
-                 std::max(vM, p.aM), nullptr, nullptr, vx));
-    else
-      RC(run_fwd(h, {{out, P_NEW, 0, 0, T}}, vM, nullptr, nullptr, vx));
-  } else {
-    RC(run_fwd(h, {{out, P_NEW, 2, 0, T}}, B, p.S1, p.S1));
-  }
+  RC(run_bwd(h, 0, T, B, p.S, p.phi, nullptr, losses, td, bx));
+  if (!bx.fuse_v0) return run_fwd(h, {{out, P_NEW, 2, 0, T}}, B, p.S1, p.S1);
+  vx.l0 = 1;
+  vx.skip = armed && r > 0 && skip_fwd ? h->skip : nullptr;
+  if (ahead)
+    return run_fwd(h, {{out, P_NEW, 0, 0, T, vM, 0}, {R_NS, P_NEW, 0, 0, T, p.aM, a_noskip},
+                       {R_NS1, P_NEW, 0, 0, T, p.aM, a_noskip}, {R_NS1T, P_TARGET, 0, 0, T, p.aM, a_noskip}},
+                   std::max(vM, p.aM), nullptr, nullptr, vx);
+  return run_fwd(h, {{out, P_NEW, 0, 0, T}}, vM, nullptr, nullptr, vx);
+}
+
+// One speculative round r of the all-task update: every policy takes its GPI next actions
+// with heads t < i seen through role `guess` (round 0: the pre-step heads), every head
+// updates from its read slot into its write slot, the post-update forward of S1 (++ s_next)
+// lands in POST_ROLE.  Only a final round runs k_ver (flag the first policy whose actions
+// were wrong; action selection): an earlier round's verdict would be overwritten unread.
+int launch_round(sfx_handle* h, const sfx_handle::Pending& p, int r, bool final) {
+  const int T = h->T, B = p.B, out = POST_ROLE;
+  TdgSpec td;
+  td.use_gpi = p.use_gpi;
+  td.guess = r == 0 ? R_S1 : POST_ROLE;
+  td.next = spec_buf(h, r);
+  td.next_stride = MMAX;
+  td.flag = &h->dout->flag;
+  td.prev = r > 0 ? spec_buf(h, r - 1) : nullptr;
+  td.skip = h->skip_rounds;
+  // the s_next row rides along in every round: one role for every round (POST_ROLE), so a head a
+  // later round skips must already have its row in the role when the final round's selection reads it
+  bool v0 = false;
+  RC(round_body(h, p, r, final, td, FwdExtra(), p.sel ? p.s_next : nullptr, true, true, p.losses, &v0));
   if (!final) return SFX_OK;
-  const bool sel = p.sel && bx.fuse_v0;
+  const bool sel = p.sel && v0;
   const bool verify = p.use_gpi != 0;
+  const float* wsel = h->w + (size_t)p.task * h->dpad;
   GpiArgs gs = gpi_args(out, B, 0, wsel, nullptr, p.q_out, p.task_out, nullptr, h->dout->sel, p.task, p.sel_use_gpi, 1);
   gs.out_ind = p.out_ind;
   // the ver launch posts the verdict to the host itself when nothing after it changes the selection
   if (verify || sel)
     RC(run_ver(h, B, verify ? T : 1, sel, out, gs, spec_buf(h, r), h->post_hout && (sel || !p.sel)));
-  if (p.sel && !bx.fuse_v0) {  // selection through the plain forward path
+  if (p.sel && !v0) {  // selection through the plain forward path
     RC(run_fwd(h, {{R_A, P_NEW, 1, 0, T}}, 1, p.s_next, nullptr));
     gs.role = R_A;
     gs.rowoff = 0;
@@ -1162,12 +1170,7 @@ int select_pick(sfx_handle* h, int task, int use_gpi, float* q, int64_t* out, co
     return SFX_OK;
   }
   RC(run_gpi(h, g));
-  if (pub && pub->res) {
-    hipLaunchKernelGGL(k_publish, dim3(1), dim3(64), 0, h->stream, (const int64_t*)out, pub->flag, pub->res, pub->dctr,
-                       pub->cancel, pub->nonfin);
-    LAUNCHCHK();
-  }
-  return SFX_OK;
+  return pub && pub->res ? run_publish(h, out, *pub) : SFX_OK;
 }
 
 // DeepSF.update_successor of one head (sfdqn.py:303-371): forwards, GPI / own-ψ next actions,
@@ -1257,23 +1260,36 @@ int select_ahead_body(sfx_handle* h, const float* s, const float* ax, const floa
 }
 
 
+// The step-start forward of an all-task step (this file's, the sharded ones of sfx_shard.inc): the
+// LMS on w[task] (task < 0: none) rides in its first launch ...
+FwdExtra lms_extra(int task, const float* phi, const float* r, float alpha) {
+  FwdExtra ex;
+  ex.lms_head = task;
+  ex.lms_phi = phi;
+  ex.lms_r = r;
+  ex.lms_alpha = alpha;
+  return ex;
+}
+// ... which forwards the minibatch into the roles round 0 reads or, when the step has none, the
+// selection row into R_A.  ex: lms_extra plus the caller's own extras
+int step_fwd(sfx_handle* h, const sfx_handle::Pending& p, const FwdExtra& ex) {
+  const int T = h->T;
+  if (!p.update) return run_fwd(h, {{R_A, P_ONLINE, 1, 0, T}}, 1, p.s_next, nullptr, ex);
+  return run_fwd(h, {{R_S, P_ONLINE, 1, 0, T}, {R_S1T, P_TARGET, 2, 0, T}, {R_S1, P_ONLINE, 2, 0, T}}, p.B, p.S, p.S1, ex);
+}
+
 int launch_step_all(sfx_handle* h, const sfx_handle::Pending& p, int lms_task, const float* lms_phi, const float* lms_r,
                     float lms_alpha, int rounds) {
-  const int T = h->T, B = p.B;
-  FwdExtra ex;
-  ex.lms_head = lms_task;
-  ex.lms_phi = lms_phi;
-  ex.lms_r = lms_r;
+  FwdExtra ex = lms_extra(lms_task, lms_phi, lms_r, lms_alpha);
   if (h->xin && lms_r == reinterpret_cast<const float*>(h->xin + 3)) {  // sfx_update_all_select, device reward
     ex.lms_r = nullptr;
     ex.lms_r_ind = h->xin + 3;
   }
-  ex.lms_alpha = lms_alpha;
   ex.flag = &h->dout->flag;
-  ex.flag_value = T;
+  ex.flag_value = h->T;
   if (!p.update) {
     const float* wsel = h->w + (size_t)p.task * h->dpad;
-    RC(run_fwd(h, {{R_A, P_ONLINE, 1, 0, T}}, 1, p.s_next, nullptr, ex));
+    RC(step_fwd(h, p, ex));
     GpiArgs gs = gpi_args(R_A, 0, 0, wsel, nullptr, p.q_out, p.task_out, nullptr, h->dout->sel, p.task,
                           p.sel_use_gpi, 1);
     gs.out_ind = p.out_ind;
@@ -1281,8 +1297,7 @@ int launch_step_all(sfx_handle* h, const sfx_handle::Pending& p, int lms_task, c
   }
   // a look-ahead step (p.pre) starts at its TD launch: the step before forwarded its minibatch
   // into these roles, its gate reset the flag and ran the LMS
-  if (!p.pre)
-    RC(run_fwd(h, {{R_S, P_ONLINE, 1, 0, T}, {R_S1T, P_TARGET, 2, 0, T}, {R_S1, P_ONLINE, 2, 0, T}}, B, p.S, p.S1, ex));
+  if (!p.pre) RC(step_fwd(h, p, ex));
   for (int r = 0; r < rounds; ++r) RC(launch_round(h, p, r, r == rounds - 1));
   return SFX_OK;
 }

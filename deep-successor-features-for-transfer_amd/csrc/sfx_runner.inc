@@ -542,14 +542,13 @@ int runner_body(sfx_runner* R, bool have, bool lms, sfx_runner::StepFlags fl = {
   const bool pre = have && fl.pre, ahead = have && fl.ahead;
   RC(runner_launch_gate(R, ahead, pre, lms));
   if (R->schedule == RUN_SHARD_TSF) return shard_tsf_body(R, have, pre, ahead);
-  if (R->schedule == RUN_SHARD) {  // the all-task step with the heads sharded over the ranks
-    // (pre: the step before forwarded this minibatch and this step's gate ran the LMS)
-    const sfx_handle::Pending p = runner_pending(R, have, pre, ahead);
-    RC(shard_begin_body(h, p, lms && !pre ? R->task : -1, at(R->lay.phi1), at(R->lay.r1), R->alpha_w));
-    const int rounds = have ? h->spec_rounds : 0;
-    for (int r = 0; r < rounds; ++r) RC(shard_round_body(h, p, r, r == rounds - 1));
-    return shard_final_body(h, p, rounds - 1, R->res, R->dctr);  // k_sfinish publishes
-  }
+  const SelPub pub{R->res, (const long long*)R->dctr, (const int*)&h->dout->flag, (const int*)h->dcancel,
+                   (const int*)h->G.nonfin};
+  // the all-task step with the heads sharded over the ranks; k_sfinish publishes
+  // (pre: the step before forwarded this minibatch and this step's gate ran the LMS)
+  if (R->schedule == RUN_SHARD)
+    return shard_step_all(h, runner_pending(R, have, pre, ahead), lms && !pre ? R->task : -1, at(R->lay.phi1),
+                          at(R->lay.r1), R->alpha_w, have ? h->spec_rounds : 0, R->res, R->dctr);
   if (R->schedule != RUN_ALL) {
     const int64_t* a = reinterpret_cast<const int64_t*>(R->dst + R->lay.a);
     const bool phis = phi_sched(R->schedule);
@@ -574,8 +573,6 @@ int runner_body(sfx_runner* R, bool have, bool lms, sfx_runner::StepFlags fl = {
     // the action for s_next sees the post-update heads: the update flips the task's slot
     const unsigned long long saved = h->mask;
     if (have) h->mask ^= 1ull << R->task;
-    const SelPub pub{R->res, (const long long*)R->dctr, (const int*)&h->dout->flag, (const int*)h->dcancel,
-                     (const int*)h->G.nonfin};
     const int rc = ahead ? select_ahead_body(h, at(R->lay.snext), at(R->lay.ax),
                                              R->schedule == RUN_TSF ? at(R->lay.axphi) : nullptr, R->B, R->task,
                                              R->sel_use_gpi, h->dout->sel, &pub)
@@ -595,13 +592,8 @@ int runner_body(sfx_runner* R, bool have, bool lms, sfx_runner::StepFlags fl = {
   h->pub_dctr = nullptr;
   h->pub_folded = false;
   RC(rc);
-  if (!folded) {  // no final k_ver with action selection in this step: publish on its own
-    hipLaunchKernelGGL(k_publish, dim3(1), dim3(64), 0, h->stream, (const int64_t*)h->dout->sel,
-                       (const int*)&h->dout->flag, R->res, (const long long*)R->dctr, (const int*)h->dcancel,
-                       (const int*)h->G.nonfin);
-    LAUNCHCHK();
-  }
-  return SFX_OK;
+  // no final k_ver with action selection in this step: publish on its own
+  return folded ? SFX_OK : run_publish(h, h->dout->sel, pub);
 }
 
 // Launch ONE graph holding `nsteps` consecutive steps (up to span_max when the runner
@@ -887,9 +879,7 @@ int runner_host_rounds(sfx_runner* R, int flag, long long* c, long long* a) {
     const GateArgs g = runner_gate(R);
     if (g.clr && hipMemsetD32Async((hipDeviceptr_t)g.clr, SORT_EMPTY, (size_t)g.nclr, h->stream) != hipSuccess)
       return SFX_E_HIP;
-    RC(shard_begin_body(h, p, -1, nullptr, nullptr, 0.f));
-    for (int rr = 0; rr < h->spec_rounds; ++rr) RC(shard_round_body(h, p, rr, rr == h->spec_rounds - 1));
-    return shard_final_body(h, p, h->spec_rounds - 1, nullptr, nullptr);
+    return shard_step_all(h, p, -1, nullptr, nullptr, 0.f, h->spec_rounds, nullptr, nullptr);
   };
   const RoundsHold hold(R);  // before the handle leaves the step stream: a drain works on that one
   if (shard && hold.drained && coll_active(h))  // a recompute would repeat its collectives on this rank only

@@ -27,26 +27,6 @@ int shard_fail_inactive(sfx_handle* h) {
   return SFX_OK;
 }
 
-int run_qmax(sfx_handle* h, int guess, int* X) {
-  const int B = h->spend.B, TA = h->T * h->A;
-  QmaxArgs Q{};
-  Q.M = B;
-  Q.Tg = h->Tg;
-  Q.off = h->off;
-  Q.guess = guess;
-  Q.rows = TA >= 256 ? 1 : std::min(B, 256 / TA);
-  Q.pol0 = 0;
-  Q.tsel = -1;
-  Q.X = X;
-  const double by = 4.0 * (double)h->Tg * B * (TA * h->d + h->A) + 4.0 * h->Tg * h->d;
-  if (wide_gpi(h))
-    launch(h, K_VER, by, SFX_WIDE(k_qmaxw), dim3(B, cdiv(h->Tg, WPC)), dim3(256), h->G, Q);
-  else
-    launch(h, K_VER, by, k_qmax, dim3(h->Tg, cdiv(B, Q.rows)), dim3(256), h->G, Q);
-  LAUNCHCHK();
-  return SFX_OK;
-}
-
 // ---- the sharded all-task env step as one stream of launches (the native runner's "sharded"
 // schedule): every collective is coll_max on h->stream, so with RCCL the whole step, all-reduces
 // included, is captured into one graph.  p: the step's staged inputs (runner_pending).
@@ -90,35 +70,25 @@ size_t shard_body(const sfx_handle* h, int B) { return (size_t)h->Tg * B * h->A;
 // the selection table; then round 0's all-reduce
 int shard_begin_body(sfx_handle* h, const sfx_handle::Pending& p, int lms_task, const float* lms_phi,
                      const float* lms_r, float lms_alpha) {
-  FwdExtra ex;
-  ex.lms_head = lms_task;
-  ex.lms_phi = lms_phi;
-  ex.lms_r = lms_r;
-  ex.lms_alpha = lms_alpha;
+  FwdExtra ex = lms_extra(lms_task, lms_phi, lms_r, lms_alpha);
   const bool fused = shard_fused(h, p.B);
-  if (!p.update) {
-    if (fused) {
-      ex.qa_role = R_A;
-      ex.qa_M = 0;
-      ex.qa_sel = h->xb[0];
-      ex.qa_row = 0;
-      ex.qa_task = p.task;
-      ex.qa_use_gpi = p.sel_use_gpi;
-    }
-    RC(run_fwd(h, {{R_A, P_ONLINE, 1, 0, h->T}}, 1, p.s_next, nullptr, ex));
-    return fused ? coll_max(h, h->xb[0], (size_t)h->Tg * h->A) : SFX_OK;
-  }
-  if (fused) {
+  if (fused && !p.update) {
+    ex.qa_role = R_A;
+    ex.qa_M = 0;
+    ex.qa_sel = h->xb[0];
+    ex.qa_row = 0;
+    ex.qa_task = p.task;
+    ex.qa_use_gpi = p.sel_use_gpi;
+  } else if (fused) {
     ex.qa_role = R_S1;
     ex.qa_M = p.B;
     ex.qa_all = h->xb[0];
     ex.qa_ge = h->xge;
+  } else if (p.update && p.pre) {
+    return SFX_OK;  // look-ahead: the step before forwarded this minibatch (runner_ahead_ok)
   }
-  if (p.pre && !fused) return SFX_OK;  // look-ahead: the step before forwarded this minibatch (runner_ahead_ok)
-  RC(run_fwd(h, {{R_S, P_ONLINE, 1, 0, h->T}, {R_S1T, P_TARGET, 2, 0, h->T}, {R_S1, P_ONLINE, 2, 0, h->T}}, p.B, p.S,
-             p.S1, ex));
-  if (!fused) return SFX_OK;
-  return coll_max(h, h->xb[0], shard_body(h, p.B));
+  RC(step_fwd(h, p, ex));
+  return fused ? coll_max(h, h->xb[0], p.update ? shard_body(h, p.B) : (size_t)h->Tg * h->A) : SFX_OK;
 }
 
 // speculative round r: (unfused: GPI maxima of every global policy over this rank's heads ->
@@ -126,85 +96,49 @@ int shard_begin_body(sfx_handle* h, const sfx_handle::Pending& p, int lms_task, 
 // S1 ++ s_next (fused: which accumulates the next round's maxima, all-reduced right after;
 // final rounds also fill the selection table)
 int shard_round_body(sfx_handle* h, const sfx_handle::Pending& p, int r, bool final) {
-  const int guess = r == 0 ? R_S1 : POST_ROLE, out = POST_ROLE;
   const bool fused = shard_fused(h, p.B);
   const size_t body = shard_body(h, p.B), tail = (size_t)h->Tg * h->A;
   int* xr = fused ? h->xb[r & 1] : h->xb[0];
   int* xn = h->xb[(r + 1) & 1];
   if (!fused) {
-    RC(shard_qmax(h, p.B, guess, xr));
+    RC(shard_qmax(h, p.B, r == 0 ? R_S1 : POST_ROLE, xr));
     RC(coll_max(h, xr, body));
   }
   TdgSpec td;
   td.use_gpi = 1;
-  td.a = p.a;
-  td.gamma = p.gamma;
   td.xmax = xr;
   td.poloff = h->off;
   td.next = spec_buf(h, r);  // local policies' next actions: round r+1 compares against them
   td.next_stride = MMAX;
   td.prev = r > 0 ? spec_buf(h, r - 1) : nullptr;
   td.skip = h->skip_rounds;
+  // a skipped head's post-update forward is skipped too: unfused, its rows of the round's role
+  // already hold what it would write; fused, its terms of the next round's maxima are replayed from
+  // the copy its last computed round stored (FwdArgs::qh)
+  const bool skip_fwd = h->skip_rounds && (!fused || h->qh);
+  FwdExtra vx;
   if (fused) {
     td.xi_src = h->xge;
     td.xi_dst = xn;
     td.xi_copy = (int)body;
     td.xi_n = (int)(body + (final ? tail : 0));
-  }
-  BwdExtra bx;
-  bx.inc_step = r == 0 ? 1 : 0;  // later rounds redo the same optimizer step
-  bx.fuse_v0 = can_fuse_v0(h, p.B + 1);
-  bx.vRole = out;
-  bx.v_x = p.S1;
-  bx.v_xn = p.s_next;
-  // look-ahead (unfused maxima only, DESIGN.md §4): the final round also forwards the next step's
-  // minibatch into the other copy of the minibatch roles; the last device round for every head
-  const int vM = p.B + 1;
-  const bool ahead = !fused && final && p.ax && p.aM > 0 && bx.fuse_v0 && can_fuse_ahead(h, vM, p.aM);
-  const int a_noskip = ahead && r <= h->spec_rounds - 1 ? 1 : 0;
-  if (ahead) {
-    bx.ax = p.ax;
-    bx.aM = p.aM;
-    bx.a_noskip = a_noskip;
-  }
-  // a skipped head's post-update forward is skipped too: unfused, its rows of the round's role
-  // already hold what it would write; fused, its terms of the next round's maxima are replayed from
-  // the copy its last computed round stored (FwdArgs::qh)
-  const bool skip_fwd = h->skip_rounds && (!fused || h->qh);
-  bx.skip_fwd = skip_fwd;
-  bool armed = false;
-  bx.skip_armed = &armed;
-  RC(run_bwd(h, 0, h->T, p.B, p.S, p.phi, nullptr, nullptr, td, bx));
-  if (bx.fuse_v0) {
-    FwdExtra vx;
-    vx.l0 = 1;
-    if (fused) {
-      vx.qa_role = out;
-      vx.qa_M = p.B;
-      vx.qa_lt = xn;
-      vx.qa_sel = final ? xn + body : nullptr;
-      vx.qa_row = p.B;
-      vx.qa_task = p.task;
-      vx.qa_use_gpi = p.sel_use_gpi;
-      if (skip_fwd) {
-        vx.qh = h->qh;
-        vx.qhs = h->qhs;
-        vx.skip = armed && r > 0 ? h->skip : nullptr;
-      }
-    } else if (skip_fwd) {
-      vx.skip = armed && r > 0 ? h->skip : nullptr;
+    vx.qa_role = POST_ROLE;
+    vx.qa_M = p.B;
+    vx.qa_lt = xn;
+    vx.qa_sel = final ? xn + body : nullptr;
+    vx.qa_row = p.B;
+    vx.qa_task = p.task;
+    vx.qa_use_gpi = p.sel_use_gpi;
+    if (skip_fwd) {
+      vx.qh = h->qh;
+      vx.qhs = h->qhs;
     }
-    if (ahead)
-      RC(run_fwd(h, {{out, P_NEW, 0, 0, h->T, vM, 0}, {R_NS, P_NEW, 0, 0, h->T, p.aM, a_noskip},
-                     {R_NS1, P_NEW, 0, 0, h->T, p.aM, a_noskip}, {R_NS1T, P_TARGET, 0, 0, h->T, p.aM, a_noskip}},
-                 std::max(vM, p.aM), nullptr, nullptr, vx));
-    else
-      RC(run_fwd(h, {{out, P_NEW, 0, 0, h->T}}, p.B + 1, nullptr, nullptr, vx));
-    if (fused) return coll_max(h, xn, body + (final ? tail : 0));
-    return SFX_OK;
   }
-  RC(run_fwd(h, {{out, P_NEW, 2, 0, h->T}}, p.B, p.S1, p.S1));
-  return run_fwd(h, {{R_A, P_NEW, 1, 0, h->T}}, 1, p.s_next, nullptr);
+  // the look-ahead with unfused maxima only (DESIGN.md §4)
+  bool v0 = false;
+  RC(round_body(h, p, r, final, td, vx, p.s_next, skip_fwd, !fused, nullptr, &v0));
+  if (!v0) return run_fwd(h, {{R_A, P_NEW, 1, 0, h->T}}, 1, p.s_next, nullptr);
+  return fused ? coll_max(h, xn, body + (final ? tail : 0)) : SFX_OK;
 }
 
 // after the last round r_last (< 0: no update this step): verification against the post-update
@@ -257,6 +191,15 @@ int shard_final_body(sfx_handle* h, const sfx_handle::Pending& p, int r_last, Ho
   launch(h, K_VER, 4.0 * (2.0 * body + (double)h->Tg * h->A), k_sfinish, dim3(1), dim3(1024), F);
   LAUNCHCHK();
   return SFX_OK;
+}
+
+// The sharded step p as the runner launches it, launch_step_all's twin: the begin, `rounds` device
+// rounds (0: no minibatch in this step) and the finish
+int shard_step_all(sfx_handle* h, const sfx_handle::Pending& p, int lms_task, const float* lms_phi, const float* lms_r,
+                   float lms_alpha, int rounds, HostResult* pub, const long long* dctr) {
+  RC(shard_begin_body(h, p, lms_task, lms_phi, lms_r, lms_alpha));
+  for (int r = 0; r < rounds; ++r) RC(shard_round_body(h, p, r, r == rounds - 1));
+  return shard_final_body(h, p, rounds - 1, pub, dctr);
 }
 
 // xb[2], xge of the sharded step (sized for T_glob, max_batch); xge follows xb[0] in one block so
@@ -341,8 +284,9 @@ int sfx_shard_begin(sfx_t h, const float* S, const int64_t* a, const float* phi,
     SFX_FAIL(SFX_E_ARG, "sfx_shard_begin: bad minibatch / next state");
   if (lms_task >= h->Tg || (lms_task >= 0 && (!lms_phi || !lms_r))) SFX_FAIL(SFX_E_ARG, "bad LMS args");
   auto& P = h->spend;
-  P = sfx_handle::ShardPending();
+  P = sfx_handle::Pending();
   P.active = true;
+  P.update = B > 0;
   P.B = B;
   P.S = S;
   P.S1 = S1;
@@ -353,16 +297,7 @@ int sfx_shard_begin(sfx_t h, const float* S, const int64_t* a, const float* phi,
   unsigned ab;
   std::memcpy(&ab, &lms_alpha, 4);
   const GraphKey key = make_key(10, {B, lms_task, (int)ab}, h->mask, {S, S1, s_next, lms_phi, lms_r});
-  return run_graph(h, key, [&]() -> int {
-    FwdExtra ex;
-    ex.lms_head = lms_task;
-    ex.lms_phi = lms_phi;
-    ex.lms_r = lms_r;
-    ex.lms_alpha = lms_alpha;
-    if (B == 0) return run_fwd(h, {{R_A, P_ONLINE, 1, 0, h->T}}, 1, s_next, nullptr, ex);
-    return run_fwd(h, {{R_S, P_ONLINE, 1, 0, h->T}, {R_S1T, P_TARGET, 2, 0, h->T}, {R_S1, P_ONLINE, 2, 0, h->T}}, B,
-                   S, S1, ex);
-  });
+  return run_graph(h, key, [&]() -> int { return step_fwd(h, P, lms_extra(lms_task, lms_phi, lms_r, lms_alpha)); });
 }
 
 int sfx_shard_td_maxima(sfx_t h, int round, int32_t* X) {
@@ -372,7 +307,7 @@ int sfx_shard_td_maxima(sfx_t h, int round, int32_t* X) {
   if (h->spend.B == 0) SFX_FAIL(SFX_E_STATE, "no minibatch in this step");
   const int guess = round == 0 ? R_S1 : POST_ROLE;
   const GraphKey key = make_key(11, {h->spend.B, guess}, h->mask, {X});
-  return run_graph(h, key, [&]() -> int { return run_qmax(h, guess, X); });
+  return run_graph(h, key, [&]() -> int { return shard_qmax(h, h->spend.B, guess, X); });
 }
 
 int sfx_shard_td_update(sfx_t h, int round, const int32_t* X) {
@@ -386,24 +321,11 @@ int sfx_shard_td_update(sfx_t h, int round, const int32_t* X) {
   return run_graph(h, key, [&]() -> int {
     TdgSpec td;
     td.use_gpi = 1;
-    td.a = P.a;
-    td.gamma = P.gamma;
     td.xmax = X;
     td.poloff = h->off;
-    BwdExtra bx;
-    bx.inc_step = round == 0 ? 1 : 0;  // later rounds redo the same optimizer step
-    bx.fuse_v0 = can_fuse_v0(h, P.B + 1);
-    bx.vRole = POST_ROLE;
-    bx.v_x = P.S1;
-    bx.v_xn = P.s_next;
-    RC(run_bwd(h, 0, h->T, P.B, P.S, P.phi, nullptr, nullptr, td, bx));
-    if (bx.fuse_v0) {
-      FwdExtra vx;
-      vx.l0 = 1;
-      return run_fwd(h, {{POST_ROLE, P_NEW, 0, 0, h->T}}, P.B + 1, nullptr, nullptr, vx);
-    }
-    RC(run_fwd(h, {{POST_ROLE, P_NEW, 2, 0, h->T}}, P.B, P.S1, P.S1));
-    return run_fwd(h, {{R_A, P_NEW, 1, 0, h->T}}, 1, P.s_next, nullptr);
+    bool v0 = false;  // no next / prev actions, no skipping, no look-ahead: the caller drives the rounds
+    RC(round_body(h, P, round, false, td, FwdExtra(), P.s_next, false, false, nullptr, &v0));
+    return v0 ? SFX_OK : run_fwd(h, {{R_A, P_NEW, 1, 0, h->T}}, 1, P.s_next, nullptr);
   });
 }
 
@@ -413,7 +335,7 @@ int sfx_shard_ver_maxima(sfx_t h, int round, int32_t* Y) {
   RC(shard_fail_inactive(h));
   if (h->spend.B == 0) SFX_FAIL(SFX_E_STATE, "no minibatch in this step");
   const GraphKey key = make_key(13, {h->spend.B, POST_ROLE}, h->mask, {Y});
-  return run_graph(h, key, [&]() -> int { return run_qmax(h, POST_ROLE, Y); });
+  return run_graph(h, key, [&]() -> int { return shard_qmax(h, h->spend.B, POST_ROLE, Y); });
 }
 
 int sfx_shard_verify(sfx_t h, const int32_t* X, const int32_t* Y, int* flag) {

@@ -120,16 +120,18 @@ def test_native_sharded_single_rank_rccl(fused, force, monkeypatch):
     _oracle_check(cfg, recs, final, heads, targets, ws)
 
 
-@pytest.mark.parametrize("t_loc,force", [(40, None), (64, 1)], ids=["40-heads", "64-heads-host-rounds"])
-def test_native_sharded_single_rank_many_heads(t_loc, force, monkeypatch):
+@pytest.mark.parametrize("t_loc,force,n_s", [(40, None, 17), (64, 1, 17), (4, 1, 70)],
+                         ids=["40-heads", "64-heads-host-rounds", "n_s70-host-rounds"])
+def test_native_sharded_single_rank_many_heads(t_loc, force, n_s, monkeypatch):
     """BASELINE config C4's 64 source tasks on ONE GPU: the sharded schedule at
     world 1 with T_loc * A > 256 takes its GPI maxima from the wide kernels (k_qmaxw: one workgroup
     per (row, 8 policies), lane = head), three device rounds by
     default (T_glob >= 16) with round skipping in the unfused TD launch (tdg_skip_report) -- through
     real RCCL all-reduces and, forced, host rounds.  Every env action bit-exact to the in-order
-    oracle."""
+    oracle.  n_s = 70 (4 heads): a fan-in past the fused layer-0 limit, so the device and host rounds'
+    post-update forward and the selection row take the plain forward path."""
     monkeypatch.setenv("SFX_RCCL_WORLD1", "1")
-    cfg = dict(SMALL, spec=dict(n_s=17, H=16, A=7, d=8, acts=("relu", "relu")), world=1, t_loc=t_loc, steps=14)
+    cfg = dict(SMALL, spec=dict(n_s=n_s, H=16, A=7, d=8, acts=("relu", "relu")), world=1, t_loc=t_loc, steps=14)
     recs, final, heads, targets, ws, stats, counters = _run_rank(0, cfg, "rccl", force_rerun=force)
     assert counters.sum() == cfg["steps"]
     if force is not None:

@@ -101,10 +101,13 @@ def _check(actions, heads, targets, ws, want, st, steps=STEPS):
     rel_close(ws, st.w, rtol=1e-5, atol=1e-7)
 
 
-@pytest.mark.parametrize("rounds", [1, 2])
-def test_single_rank_shard_protocol(rounds):
-    actions, heads, targets, ws, stats = _run_rank(0, 1, rounds, lambda t: None)
-    want, st = _oracle()
+@pytest.mark.parametrize("rounds,n_s", [(1, 17), (2, 17), (2, 70)], ids=["1", "2", "2-n_s70"])
+def test_single_rank_shard_protocol(rounds, n_s):
+    """n_s = 70: a fan-in past the fused layer-0 limit, so every round's post-update forward and the
+    selection row take the plain forward path."""
+    cfg = dict(SMALL, spec=dict(SPEC, n_s=n_s))
+    actions, heads, targets, ws, stats = _run_rank(0, 1, rounds, lambda t: None, cfg)
+    want, st = _oracle(cfg)
     _check(actions, heads, targets, ws, want, st)
     assert stats["steps"] == STEPS - 1
 
