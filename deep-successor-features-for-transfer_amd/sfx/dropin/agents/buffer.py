@@ -113,10 +113,6 @@ class ReplayBuffer:
         else:
             row.copy_(torch.as_tensor(np.asarray(x, dtype=np.float32)).reshape(row.shape))
 
-    def _dev_index(self) -> int:
-        i = self.device.index
-        return torch.cuda.current_device() if i is None else i
-
     def _native(self, state, action, reward, next_state) -> bool:
         """Device tensors of the ring's dtypes, on the ring's device, contiguous: libsfx's one-launch
         row copy applies."""

@@ -208,9 +208,6 @@ class SFEngine:
             t = t.reshape(shape)
         return t.contiguous()
 
-    def _l(self, x) -> torch.Tensor:
-        return self._h2d(x, torch.long).reshape(-1).contiguous()
-
     def _batch_in(self, s, s1, a, phi, gamma, r=None):
         """A minibatch's device inputs (s, s1 [B, n_s], a [B] int64, φ [B, d], γ [B], r [B] or None),
         one staged copy for all of them."""

@@ -95,7 +95,7 @@ def schedule(E, horizon, eps, seed):
 
 
 def python_phase(eng, env, W, Wb, explore, horizon):
-    """The phase as a Python loop over the existing calls, as sfx.lockstep._phi_group makes them: per lockstep
+    """The phase as a Python loop over the existing calls, as sfx.lockstep's SF-φ kind makes them: per lockstep
     step one phi_test_actions and one phi_test_updates on the rows that still run (gathered, then scattered)."""
     E, dev = W.shape[0], eng.device
     S = np.stack([env.reset(e) for e in range(E)])

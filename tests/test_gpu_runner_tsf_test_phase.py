@@ -121,7 +121,7 @@ def lr_omega(k):
 
 def python_phase(eng, env, W, Om, M, opt, T, d, explore, horizon):
     """The phase as a Python loop over the existing calls, on the live rows only (compacted as
-    sfx.lockstep._tsf_group does): tsf_test_actions(S), the env, tsf_test_actions(S1) with the explored entries
+    sfx.lockstep's TSF kind does): tsf_test_actions(S), the env, tsf_test_actions(S1) with the explored entries
     overwritten, tsf_test_updates with rowp from sfx_tsf_test_lr_omega.  W / Om / M (device, strided) and opt are
     updated in place."""
     E, dev = W.shape[0], eng.device

@@ -438,6 +438,68 @@ def test_tsf_lockstep_declared_endless_task_that_ends_stops_there():
         assert torch.equal(oa.detach(), ob.detach())
 
 
+# ---- the engine calls of a lockstep step, for the three kinds of phase ----
+
+_STEP_CALLS = {"sf": ("test_actions", "test_reward_updates"),
+               "tsf": ("tsf_test_actions", "tsf_test_actions", "tsf_test_updates"),
+               "phi": ("phi_test_actions", "phi_test_updates")}
+
+
+def _recorded(eng, names, log):
+    """Wrap the engine's calls: log (name, rows) and require every tensor argument to carry the same rows."""
+    for name in set(names):
+        def call(*args, _f=getattr(eng, name), _name=name, **kw):
+            rows = {x.shape[0] for x in list(args) + list(kw.values()) if torch.is_tensor(x)}
+            assert len(rows) == 1, (_name, rows)
+            log.append((_name, rows.pop()))
+            return _f(*args, **kw)
+        setattr(eng, name, call)
+
+
+@pytest.mark.parametrize("E,ends", [(3, None), (3, (1, 2)), (6, None), (6, (4, 3))])
+@pytest.mark.parametrize("kind", ["sf", "tsf", "phi"])
+def test_lockstep_step_makes_its_engine_calls_over_the_live_rows(kind, E, ends):
+    """A phase of T steps makes exactly its kind's calls per lockstep step, in order, each with len(live) rows:
+    after task e has ended at its step k (``ends`` = (e, k)) the later calls of its group carry one row fewer; more
+    tasks than the cap (4 for the TSF and φ stand-ins; the SF kind asks for all E rows) run as consecutive groups,
+    each with its own T steps."""
+    import contextlib
+
+    from sfx import lockstep
+
+    T, cap = 5, E if kind == "sf" else 4
+    at = [ends[1] if ends and e == ends[0] else None for e in range(E)]
+    if kind == "sf":
+        sf, agent, tasks = _setup(E, T, 0.2)
+        eng, run, mapper = sf.eng, lockstep.test_tasks_lockstep, type(agent).update_test_reward_mapper
+        _ending(tasks, at)
+        mapper.__sfx_mapper__ = "sgd"
+    elif kind == "tsf":
+        agent, tasks = _tsf_setup(E, T, 0.2, 7)
+        eng, run = agent.sf._eng, lockstep.test_tasks_lockstep_tsf
+        _ending(tasks, at)
+    else:
+        from tests import test_phi_lockstep as P
+
+        agent, tasks = P.fresh(P.make_state(20, 1, seed=91), E, 0.2, steps=T, ends_at=dict([ends] if ends else []))
+        eng, run = agent.sf.eng, lockstep.test_tasks_lockstep_phi
+    log = []
+    _recorded(eng, _STEP_CALLS[kind], log)
+    try:
+        with pytest.warns(RuntimeWarning, match="declared never to end") if ends else contextlib.nullcontext():
+            run(agent, tasks, episodes_end=False)
+    finally:
+        if kind == "sf":
+            del mapper.__sfx_mapper__
+    want = []
+    for lo in range(0, E, cap):
+        group = range(lo, min(E, lo + cap))
+        for j in range(T):
+            live = sum(1 for e in group if at[e] is None or j < at[e])
+            want += [(name, live) for name in _STEP_CALLS[kind]]
+    assert log == want
+
+
 def test_tsf_test_state_survives_sf_reset():
     """the Adam state of each TSF test task's {w, ω} is keyed by the ω tensor object
     (weakly) and survives DeepTSF.reset() -- agent.reset() of a second trial; the reference keeps

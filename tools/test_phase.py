@@ -12,7 +12,6 @@ reward models initialised as in train (:87-98).
 from __future__ import annotations
 
 import random
-import time
 
 import numpy as np
 import torch
@@ -59,22 +58,16 @@ class ActionEnv:
         return torch.tanh(torch.from_numpy(self.P).to(s1.device) @ s1.reshape(-1))
 
 
-class _Log:
-    def __init__(self):
-        self.lines = []
-
-    def log_target_error_progress(self, d):
-        self.lines.append(d)
-
-
 class EvalAgent:
     """The SFDQN members of the test phase (agents/sfdqn.py), over the drop-in DeepSF."""
 
     def __init__(self, sf, n_actions, T, test_tasks, test_epsilon=0.03, device=None):
+        from tools.phase_common import Log
+
         self.sf, self.n_actions, self.T, self.test_epsilon = sf, n_actions, T, test_epsilon
         self.device = device
         self.encoding = lambda s: s
-        self.logger = _Log()
+        self.logger = Log()
         self.total_training_steps = 0
         self.test_tasks_weights = []
         for task in test_tasks:  # agents/sfdqn.py:87-98
@@ -163,31 +156,23 @@ def run_phase(agent, tasks, lockstep: bool):
 
 
 def measure(lockstep: bool, E=8, ep_len=50, phases=4, **kw) -> dict:
+    from tools.phase_common import timed
+
     sf, agent, tasks = make(E=E, ep_len=ep_len, device_mapper=lockstep, **kw)
-    run_phase(agent, tasks, lockstep)  # warm-up phase (graphs captured)
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(phases):
-        run_phase(agent, tasks, lockstep)
-    torch.cuda.synchronize()
-    dt = time.perf_counter() - t0
-    sf._close()
-    n = phases * E * ep_len
-    return {"value": round(n / dt, 2), "unit": "test env steps/s", "ms_per_step": round(1000.0 * dt / n, 4),
-            "steps": n, "dtype": "fp32",
-            "path": ("sfx.lockstep: E test tasks per sfx_test_actions launch set, their reward models' SGD steps in "
-                     "one sfx_test_reward_updates launch" if lockstep else
-                     "the reference's sequential test_agent loop over the drop-in get_successors") +
-                    f" (E={E} test tasks, {ep_len}-step episodes, T=8 heads, H=256)"}
+    return timed(lambda: run_phase(agent, tasks, lockstep), sf._close, phases * E * ep_len, phases,
+                 ("sfx.lockstep: E test tasks per sfx_test_actions launch set, their reward models' SGD steps in "
+                  "one sfx_test_reward_updates launch" if lockstep else
+                  "the reference's sequential test_agent loop over the drop-in get_successors") +
+                 f" (E={E} test tasks, {ep_len}-step episodes, T=8 heads, H=256)")
 
 
 if __name__ == "__main__":
-    import json
     import os
     import sys
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     sys.path.insert(0, os.path.join(root, "deep-successor-features-for-transfer_amd"))
     sys.path.insert(0, root)
-    for ls in (False, True):
-        print(json.dumps({"lockstep" if ls else "sequential": measure(ls)}), flush=True)
+    from tools.phase_common import main
+
+    main(measure)

@@ -13,21 +13,9 @@ and update_test_reward_mapper are the drop-in's bound methods.
 from __future__ import annotations
 
 import random
-import time
 
 import numpy as np
 import torch
-
-
-class _Log:
-    def __init__(self):
-        self.lines = []
-
-    def log_target_error_progress(self, d):
-        self.lines.append(("err", d))
-
-    def log_omegas_learning_rate(self, lr, i, t):
-        self.lines.append(("lr", lr, i, t))
 
 
 class TsfSF:
@@ -59,11 +47,12 @@ class TsfEvalAgent:
     def __init__(self, sf, n_actions, T, test_tasks, n_heads, test_epsilon=0.03, device=None, lr_w=1e-3,
                  lr_o=5e-3, decay=0.01, wd_w=1e-4, wd_o=1e-5, total_training_steps=0):
         from sfx.dropin import bind
+        from tools.phase_common import Log
 
         self._bind = bind
         self.sf, self.n_actions, self.T, self.test_epsilon, self.device = sf, n_actions, T, test_epsilon, device
         self.encoding = lambda s: s
-        self.logger = _Log()
+        self.logger = Log(tagged=True)
         self.total_training_steps = total_training_steps
         self.gamma = 0.9
         self.h_function = object()
@@ -167,36 +156,28 @@ def run_phase(agent, tasks, lockstep: bool):
 def measure(lockstep: bool, E=8, ep_len=50, phases=4, **kw) -> dict:
     """Test env-steps/s of the TSF test phase at the Hopper TSF shape (C3: 16 heads, H = 256,
     A = 27, d = 50, G = 100, K = 3 planar layers)."""
+    from tools.phase_common import timed
+
     shape = dict(T_heads=16, n_s=11, H=256, A=27, d=50, G=100, K=3)
     shape.update(kw)
     # total_training_steps not a multiple of 1000: the reference's diagnostic prints stay off
     sf, agent, tasks = make(E=E, ep_len=ep_len, total_training_steps=1, **shape)
-    run_phase(agent, tasks, lockstep)  # warm-up phase
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(phases):
-        run_phase(agent, tasks, lockstep)
-    torch.cuda.synchronize()
-    dt = time.perf_counter() - t0
-    sf._eng.close()
-    n = phases * E * ep_len
-    return {"value": round(n / dt, 2), "unit": "test env steps/s", "ms_per_step": round(1000.0 * dt / n, 4),
-            "steps": n, "dtype": "fp32",
-            "path": ("sfx.lockstep.test_tasks_lockstep_tsf: E TSF test tasks per sfx_tsf_test_actions / "
-                     "sfx_tsf_test_updates launch set" if lockstep else
-                     "the reference's sequential TSF test_agent loop over the drop-in's per-call "
-                     "sfx_tsf_test_action / sfx_tsf_test_update") +
-                    f" (E={E} test tasks, {ep_len}-step episodes, T={shape['T_heads']} heads, H={shape['H']}, "
-                    f"A={shape['A']}, d={shape['d']}, G={shape['G']}, K={shape['K']})"}
+    return timed(lambda: run_phase(agent, tasks, lockstep), sf._eng.close, phases * E * ep_len, phases,
+                 ("sfx.lockstep.test_tasks_lockstep_tsf: E TSF test tasks per sfx_tsf_test_actions / "
+                  "sfx_tsf_test_updates launch set" if lockstep else
+                  "the reference's sequential TSF test_agent loop over the drop-in's per-call "
+                  "sfx_tsf_test_action / sfx_tsf_test_update") +
+                 f" (E={E} test tasks, {ep_len}-step episodes, T={shape['T_heads']} heads, H={shape['H']}, "
+                 f"A={shape['A']}, d={shape['d']}, G={shape['G']}, K={shape['K']})")
 
 
 if __name__ == "__main__":
-    import json
     import os
     import sys
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     sys.path.insert(0, os.path.join(root, "deep-successor-features-for-transfer_amd"))
     sys.path.insert(0, root)
-    for ls in (False, True):
-        print(json.dumps({"lockstep" if ls else "sequential": measure(ls)}), flush=True)
+    from tools.phase_common import main
+
+    main(measure)
