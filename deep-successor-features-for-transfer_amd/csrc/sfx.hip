@@ -1135,42 +1135,39 @@ int select_body(sfx_handle* h, const float* s, int task, int use_gpi, float* q, 
 // the choice from role R_A row 0 (GPI with w of `task`, or `task`'s own q) and the publication
 int select_pick(sfx_handle* h, int task, int use_gpi, float* q, int64_t* out, const SelPub* pub,
                 const TsfTail* tail, const float* qb) {
-  if (qb && (tail || h->T > 64 || h->A > 256)) SFX_FAIL(SFX_E_STATE, "biased selection: only the one-state k_sel1m takes a bias");
+  if (qb && tail) SFX_FAIL(SFX_E_STATE, "biased selection: only the one-state k_sel1m takes a bias");
   const GpiArgs g = gpi_args(R_A, 0, 0, h->w + (size_t)task * h->dpad, nullptr, q, nullptr, nullptr, out, task, use_gpi, 1);
   const int TA = h->T * h->A;
-  if (h->T <= 64 && h->A <= 256) {  // one workgroup per head, the last one picks
-    const SelPub P = pub ? *pub : SelPub{};
-    const dim3 grid(h->T), block((unsigned)(cdiv(h->A, 64) * 64));
-    const double by = 4.0 * ((double)TA * h->d + h->d + (q ? TA : 0));
-    if (tail) {  // the TSF tail's workgroups first, 256-thread workgroups
-      void (*k)(Geo, GpiArgs, SelPub, SelScratch*, TsfArgs, const float*, int) = nullptr;
-      const int vw = h->d % 4 == 0 ? 4 : h->d % 2 == 0 ? 2 : 1;
-      const int np = tail->A.np;
+  // one workgroup per head (T <= 64, A <= AMAX: sfx_create), the last one picks
+  const SelPub P = pub ? *pub : SelPub{};
+  const dim3 grid(h->T), block((unsigned)(cdiv(h->A, 64) * 64));
+  const double by = 4.0 * ((double)TA * h->d + h->d + (q ? TA : 0));
+  if (tail) {  // the TSF tail's workgroups first, 256-thread workgroups
+    void (*k)(Geo, GpiArgs, SelPub, SelScratch*, TsfArgs, const float*, int) = nullptr;
+    const int vw = h->d % 4 == 0 ? 4 : h->d % 2 == 0 ? 2 : 1;
+    const int np = tail->A.np;
 #define SFX_SEL_TAIL(V) \
   k = np == 4 ? k_sel1m_tsft<V, 4> : np == 8 ? k_sel1m_tsft<V, 8> : np == 16 ? k_sel1m_tsft<V, 16> : k_sel1m_tsft<V, 32>
-      if (vw == 4)
-        SFX_SEL_TAIL(4);
-      else if (vw == 2)
-        SFX_SEL_TAIL(2);
-      else
-        SFX_SEL_TAIL(1);
-#undef SFX_SEL_TAIL
-      launch(h, K_GPI, by + tail->bytes, k, dim3(tail->nblk + h->T), dim3(256), h->G, g, P, h->selk, tail->A,
-             tail->gfl, tail->nblk);
-      LAUNCHCHK();
-      return SFX_OK;
-    }
-    if (h->d % 4 == 0)
-      launch(h, K_GPI, by, k_sel1m<4>, grid, block, h->G, g, P, h->selk, qb);
-    else if (h->d % 2 == 0)
-      launch(h, K_GPI, by, k_sel1m<2>, grid, block, h->G, g, P, h->selk, qb);
+    if (vw == 4)
+      SFX_SEL_TAIL(4);
+    else if (vw == 2)
+      SFX_SEL_TAIL(2);
     else
-      launch(h, K_GPI, by, k_sel1m<1>, grid, block, h->G, g, P, h->selk, qb);
+      SFX_SEL_TAIL(1);
+#undef SFX_SEL_TAIL
+    launch(h, K_GPI, by + tail->bytes, k, dim3(tail->nblk + h->T), dim3(256), h->G, g, P, h->selk, tail->A,
+           tail->gfl, tail->nblk);
     LAUNCHCHK();
     return SFX_OK;
   }
-  RC(run_gpi(h, g));
-  return pub && pub->res ? run_publish(h, out, *pub) : SFX_OK;
+  if (h->d % 4 == 0)
+    launch(h, K_GPI, by, k_sel1m<4>, grid, block, h->G, g, P, h->selk, qb);
+  else if (h->d % 2 == 0)
+    launch(h, K_GPI, by, k_sel1m<2>, grid, block, h->G, g, P, h->selk, qb);
+  else
+    launch(h, K_GPI, by, k_sel1m<1>, grid, block, h->G, g, P, h->selk, qb);
+  LAUNCHCHK();
+  return SFX_OK;
 }
 
 // DeepSF.update_successor of one head (sfdqn.py:303-371): forwards, GPI / own-ψ next actions,
@@ -1241,8 +1238,7 @@ int select_ahead_body(sfx_handle* h, const float* s, const float* ax, const floa
   // TSF: the chains in the first launch, the Linear of g and φ̃ (the tail) in the selection
   // launch when it can take them, so they run beside the selection instead of after the chains
   TsfTail tail;
-  const bool split = axphi && !pick && task >= 0 && T <= 64 && h->A <= 256 &&
-                     tsf_tail_rider(h, task, B, S, S1, axphi, &tail);
+  const bool split = axphi && !pick && task >= 0 && tsf_tail_rider(h, task, B, S, S1, axphi, &tail);
   if (axphi && task >= 0)
     RC(tsf_fwd_with(h, task, B, S, S1, axphi, early, s, split ? 1 : 0));
   else
@@ -1523,8 +1519,8 @@ int sfx_create(sfx_t* out, int T, int n_s, int H, int n_hidden, const int* acts,
   if (T < 1 || T > 64 || n_s < 1 || H < 1 || n_hidden < 0 || n_hidden + 2 > NLMAX || A < 1 || d < 1 ||
       max_batch < 1)
     SFX_FAIL(SFX_E_ARG, "bad geometry (1 <= T <= 64 heads per handle)");
-  if (d > DMAX || max_batch + 1 > MMAX || (long)T * A > QMAX || (long)A * d > OMAX)
-    SFX_FAIL(SFX_E_ARG, "geometry exceeds kernel limits (d<=256, batch<1024, T*A<=8192, A*d<=4096)");
+  if (d > DMAX || max_batch + 1 > MMAX || A > AMAX || (long)T * A > QMAX || (long)A * d > OMAX)
+    SFX_FAIL(SFX_E_ARG, "geometry exceeds kernel limits (d<=256, batch<1024, A<=256, T*A<=8192, A*d<=4096)");
   for (int i = 0; i < n_hidden; ++i)
     if (!acts || acts[i] < ACT_NONE || acts[i] > ACT_TANH) SFX_FAIL(SFX_E_ARG, "bad activation code");
   HIPCHK(hipSetDevice(device));

@@ -31,6 +31,7 @@ constexpr int NLMAX = 8;      // Linear layers per head (n_hidden <= 6)
 constexpr int MT = 32;        // minibatch rows per tile
 constexpr int QMAX = 8192;    // T*A entries of the per-row GPI scratch in LDS
 constexpr int OMAX = 4096;    // A*d (row of a ψ output) held in LDS
+constexpr int AMAX = 256;     // actions A: the per-action maxima of a GPI row held in LDS
 constexpr int DMAX = 256;     // feature dimension d
 constexpr int MMAX = 1024;    // rows of one update
 constexpr int KFUSE = 64;     // layer-0 fan-in up to which the post-update forward is fused
@@ -1071,7 +1072,7 @@ __global__ __launch_bounds__(256) void k_tdg(Geo G, TdgArgs A) {
   __shared__ float s_w[DMAX];
   __shared__ float s_q[QMAX];
   __shared__ float s_t[OMAX];  // ψ⁻_i(s1_b) row
-  __shared__ float s_m[256];
+  __shared__ float s_m[AMAX];
   __shared__ float s_sq[DMAX];
   __shared__ int s_next;
   const float* wrow = G.w + (long long)pol * G.dpad;
@@ -2280,7 +2281,7 @@ __device__ void gpi_row(const Geo& G, const GpiArgs& A0, int b) {
   const int T = G.T, Aa = G.A, d = G.d, O = G.O, NLm = G.lastOff, TA = T * Aa;
   __shared__ float s_q[QMAX];
   __shared__ float s_w[DMAX];
-  __shared__ float s_mt[256], s_ma[256];
+  __shared__ float s_mt[256], s_ma[AMAX];
   const long long ob = (long long)(A.row0 + b);
   const int lb = A.rowoff + b;
   const FDiv fA = fdiv(Aa);

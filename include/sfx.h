@@ -58,6 +58,9 @@ int sfx_check_failures(long long* count, long long* first_host, int reset);
  * (the lambda of main_sfdqn_torch.py:44-78, built per task by DeepSF.build_successor,
  * features/deep.py:39-78 / sfdqn.py:242-288).  max_batch bounds the minibatch rows of
  * one update (reference buffer n_batch=32, configs/reacher.cfg:265-267).
+ * Limits (SFX_E_ARG, "geometry" in the message): 1 <= T <= 64, n_hidden <= 6, d <= 256,
+ * max_batch < 1024, A <= 256 (the per-action GPI maxima of a row are held in LDS; the
+ * reference's largest A is 27), T*A <= 8192, A*d <= 4096.
  * stream: hipStream_t the handle launches on (NULL = legacy default stream).
  */
 int sfx_create(sfx_t* out, int T, int n_s, int H, int n_hidden, const int* acts_host, int A,

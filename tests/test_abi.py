@@ -41,6 +41,18 @@ def test_version_and_error_strings():
     assert b"geometry" in _lib.lib.sfx_last_error()
 
 
+def test_create_refuses_more_than_256_actions():
+    """A = 257 passes every product limit (T·A = 257, A·d = 257) but not the action limit: the per-action GPI maxima
+    of a row live in 256 floats of LDS.  A = 256 gets past the argument checks (not created here: that needs a GPU)."""
+    from sfx import _lib
+
+    h = ctypes.c_void_p()
+    rc = _lib.lib.sfx_create(ctypes.byref(h), 1, 1, 1, 0, None, 257, 1, 1, 0, None)
+    assert rc != 0 and not h.value
+    msg = _lib.lib.sfx_last_error()
+    assert b"geometry" in msg and b"A<=256" in msg
+
+
 def test_kernels_compiled_for_gfx950():
     from sfx import _lib
 

@@ -120,18 +120,24 @@ def test_native_sharded_single_rank_rccl(fused, force, monkeypatch):
     _oracle_check(cfg, recs, final, heads, targets, ws)
 
 
-@pytest.mark.parametrize("t_loc,force,n_s", [(40, None, 17), (64, 1, 17), (4, 1, 70)],
-                         ids=["40-heads", "64-heads-host-rounds", "n_s70-host-rounds"])
-def test_native_sharded_single_rank_many_heads(t_loc, force, n_s, monkeypatch):
+@pytest.mark.parametrize("t_loc,force,n_s,A,d",
+                         [(40, None, 17, 7, 8), (64, 1, 17, 7, 8), (4, 1, 70, 7, 8), (33, None, 17, 9, 12),
+                          (9, 1, 17, 32, 4), (40, None, 17, 7, 6), (6, None, 17, 9, 12)],
+                         ids=["40-heads", "64-heads-host-rounds", "n_s70-host-rounds", "33-heads-a9-d12",
+                              "9-heads-a32-d4-host-rounds", "40-heads-d6", "6-heads-a9-d12"])
+def test_native_sharded_single_rank_many_heads(t_loc, force, n_s, A, d, monkeypatch):
     """BASELINE config C4's 64 source tasks on ONE GPU: the sharded schedule at
     world 1 with T_loc * A > 256 takes its GPI maxima from the wide kernels (k_qmaxw: one workgroup
     per (row, 8 policies), lane = head), three device rounds by
     default (T_glob >= 16) with round skipping in the unfused TD launch (tdg_skip_report) -- through
     real RCCL all-reduces and, forced, host rounds.  Every env action bit-exact to the in-order
     oracle.  n_s = 70 (4 heads): a fan-in past the fused layer-0 limit, so the device and host rounds'
-    post-update forward and the selection row take the plain forward path."""
+    post-update forward and the selection row take the plain forward path.  The shapes of
+    tests/gpi_ref.py that the sharded maxima dispatch on: A = 9, d = 12 at 33 heads (k_qmaxw<3>, a
+    partial last chunk) and at 6 heads (k_qmax, qdots_vec<4,4>), A = 32, d = 4 (k_qmaxw<1>), d = 6 at 40
+    heads (k_qmax's scalar loop, two passes)."""
     monkeypatch.setenv("SFX_RCCL_WORLD1", "1")
-    cfg = dict(SMALL, spec=dict(n_s=n_s, H=16, A=7, d=8, acts=("relu", "relu")), world=1, t_loc=t_loc, steps=14)
+    cfg = dict(SMALL, spec=dict(n_s=n_s, H=16, A=A, d=d, acts=("relu", "relu")), world=1, t_loc=t_loc, steps=14)
     recs, final, heads, targets, ws, stats, counters = _run_rank(0, cfg, "rccl", force_rerun=force)
     assert counters.sum() == cfg["steps"]
     if force is not None:
