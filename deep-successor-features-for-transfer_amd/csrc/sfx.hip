@@ -567,10 +567,13 @@ int run_fwd(sfx_handle* h, std::initializer_list<FwdGroup> groups, int M, const 
                grid, dim3(64 * FWD_WAVES), h->G, F);
     } else {  // (the tpw rule above requires the vector path)
       const bool vec = (L.K % 32) == 0 && aligned;
+      // layer 0 keeps fp32 operands in bf16 mode, as it does in-tile (the fused launch above) and inside
+      // the dW tiles (fuse_v0): a head's layer 0 is the same product wherever it runs
+      const bool bf = h->bf16 && l > 0;
       launch(h, K_FWD, by,
              !vec ? k_fwd<false, false>
-                  : tp2 ? (h->bf16 ? k_fwd<true, false, true, 2> : k_fwd<true, false, false, 2>)
-                        : (h->bf16 ? k_fwd<true, false, true> : k_fwd<true, false>),
+                  : tp2 ? (bf ? k_fwd<true, false, true, 2> : k_fwd<true, false, false, 2>)
+                        : (bf ? k_fwd<true, false, true> : k_fwd<true, false>),
              grid, dim3(64 * FWD_WAVES), h->G, F);
     }
   }
@@ -2224,6 +2227,8 @@ int sfx_sync_target(sfx_t h, int t) {
   if (!valid_head(h, t)) SFX_FAIL(SFX_E_ARG, "bad head");
   touch(h);
   HIPCHK(hipMemcpyAsync(h->target_of(t), h->online_cur(t), sizeof(float) * h->P, hipMemcpyDeviceToDevice, h->stream));
+  if (h->bf16)  // the target's bf16 copy follows, as in maybe_sync_target
+    HIPCHK(hipMemcpyAsync(h->tg16_of(t), h->on16_cur(t), sizeof(__bf16) * h->P, hipMemcpyDeviceToDevice, h->stream));
   return SFX_OK;
 }
 

@@ -170,11 +170,12 @@ def _leaf(x):
 # ---------------------------------------------------------------------------------------------
 # networks (forward only; autograd does the rest)
 # ---------------------------------------------------------------------------------------------
-def mlp(flat, dims, acts, X, pre: Optional[list] = None):
-    """Packed Linears (W [out][in], b [out]) with `acts` after each; ReLU pre-activations appended to pre."""
+def mlp(flat, dims, acts, X, pre: Optional[list] = None, linear=F.linear):
+    """Packed Linears (W [out][in], b [out]) with `acts` after each; ReLU pre-activations appended to pre.
+    linear: the Linear itself, called once per layer in order (tests/bf16_ref.py: the bf16 operand emulation)."""
     y, off = X, 0
     for (o, i), a in zip(dims, acts):
-        y = F.linear(y, flat[off:off + o * i].view(o, i), flat[off + o * i:off + o * i + o])
+        y = linear(y, flat[off:off + o * i].view(o, i), flat[off + o * i:off + o * i + o])
         off += o * i + o
         if a == "relu":
             if pre is not None:
@@ -190,9 +191,9 @@ def _psi_layout(spec):
     return dims, (None,) + tuple(spec.acts) + (None,)
 
 
-def psi(flat, spec, X, pre=None):
+def psi(flat, spec, X, pre=None, linear=F.linear):
     """ψ(X) of one head [B, A, d]; spec: anything with n_s, H, A, d, acts (oracle Spec, tsf_phi_ref Net)."""
-    return mlp(flat, *_psi_layout(spec), X, pre).view(X.shape[0], spec.A, spec.d)
+    return mlp(flat, *_psi_layout(spec), X, pre, linear).view(X.shape[0], spec.A, spec.d)
 
 
 def _phi_layout(net: TP.Net):
@@ -232,10 +233,11 @@ def clear_kinks(flat, dims, acts, X, margin: float = MARGIN):
     return flat
 
 
-def next_actions_of(online, w_i, wb, spec, s1, i: int, use_gpi: bool):
+def next_actions_of(online, w_i, wb, spec, s1, i: int, use_gpi: bool, make_linear=None):
     """argmax_a max_t (ψ_t(s1)[a]·w_i + b) over all heads (GPI) or head i -> (actions [B], top-2 gap / max |q|)."""
     heads = range(online.shape[0]) if use_gpi else [i]
-    psi1 = torch.stack([psi(online[t], spec, s1) for t in heads], dim=1)
+    lin = make_linear or (lambda: F.linear)
+    psi1 = torch.stack([psi(online[t], spec, s1, linear=lin()) for t in heads], dim=1)
     q = torch.matmul(psi1, w_i.reshape(-1, 1))[..., 0] + wb
     x = q.max(dim=1).values
     top = torch.topk(x, 2, dim=1).values
@@ -262,20 +264,22 @@ def _info(nxt, gap, pre, td, huber=0.0) -> Info:
 # ---------------------------------------------------------------------------------------------
 # ψ paths: sfx_update, and one head of the all-task step
 # ---------------------------------------------------------------------------------------------
-def sf_grads(st, spec, batch, i: int, use_gpi: bool = True, huber: float = 0.0, next_actions=None):
+def sf_grads(st, spec, batch, i: int, use_gpi: bool = True, huber: float = 0.0, next_actions=None, make_linear=None):
     """DeepSF.update_successor: l1 (+ l2 = MSE(w_i·φ, r) when r is given).  st: dict(online, target, w);
-    batch = (s, a, r or None, φ, s1, γ) -> ({psi, [w]}, Info)."""
+    batch = (s, a, r or None, φ, s1, γ) -> ({psi, [w]}, Info).  make_linear: called once per network forward
+    for its `linear=` argument (None: F.linear)."""
     s, a, r, phi, s1, gamma = batch
     B = s.shape[0]
     idx = torch.arange(B)
+    lin = make_linear or (lambda: F.linear)
     with torch.no_grad():
-        nxt, gap = next_actions_of(st["online"], st["w"][i], 0.0, spec, s1, i, use_gpi)
+        nxt, gap = next_actions_of(st["online"], st["w"][i], 0.0, spec, s1, i, use_gpi, make_linear)
         if next_actions is not None:
             nxt = torch.as_tensor(next_actions)
-        targets = phi + gamma.reshape(-1, 1) * psi(st["target"][i], spec, s1)[idx, nxt, :]
+        targets = phi + gamma.reshape(-1, 1) * psi(st["target"][i], spec, s1, linear=lin())[idx, nxt, :]
     pt, wi = _leaf(st["online"][i]), _leaf(st["w"][i])
     pre = []
-    cur = psi(pt, spec, s, pre)
+    cur = psi(pt, spec, s, pre, linear=lin())
     loss = td_loss(cur, a, targets, huber)
     if r is not None:
         loss = loss + F.mse_loss(F.linear(phi, wi.reshape(1, -1)), r.reshape(B, 1))
